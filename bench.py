@@ -2,14 +2,17 @@
 """
 bench.py -- samples/sec (+ bits/dim) of one training step of the flow hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2] [--no-graph] [--skip-cpu]
+    python bench.py --gpus N --steps K --warmup W [--config c2] [--no-graph] [--dump-outputs DIR] [--full [--skip-cpu]]
 
 A "step" is one full pass of the hot path over one batch of synthetic input: forward flow + log-det, NLL,
 autograd backward through every transform kernel, gradient all-reduce (N > 1), Adam -- main.py:78-92.
 Default workloads = the two configs BASELINE.json's metric is quoted on: Glow CIFAR-10 (3,32,32) L=3 K=32, batch 64 per GPU
 (= 512 over 8, configs[3]) on the top level of the line, and RealNVP moons-2D K=32 batch 256 (configs[0]) under "also".
-`--config c1..c5` measures one workload.  `--gpus N` outside torchrun re-executes itself under torch.distributed.run.
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`, `cpu_baseline` and `parity` objects.
+`--config c1..c5` measures one workload.  `--gpus N` outside torchrun starts itself again under torch.distributed.run.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times K steps of the one workload and prints the line; `--full` adds
+the other workloads under "also" (default workload only), the `roofline`, `cpu_baseline` and `parity` objects, the event-timed
+median, the forward / inverse rates and the detail file.  `--dump-outputs DIR` writes what the last timed step returned as .npy files;
+such a run times the kernels' ordered mode (see main) so that its outputs are the same from run to run.
 
 Timed region: inputs already resident in HBM; barrier + synchronize on both sides; max over ranks.
 """
@@ -52,6 +55,7 @@ CONFIGS = {
                      global_batch=512, desc='RealNVP CIFAR-shape (3,32,32) layers=32 batch 64 per GPU', cpu_threads=16),
 }
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured float4 copy)
+DUMP_CAP_BYTES = 48 << 20      # --dump-outputs: bytes of z written at most (the files together stay under 64 MB)
 
 
 def parse():
@@ -60,14 +64,21 @@ def parse():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--config', default=None, choices=sorted(CONFIGS),
-                    help='one workload; default: c4 (Glow CIFAR-10) on the top level + c1 (RealNVP moons) under "also"')
+                    help='one workload; default: c4 (Glow CIFAR-10), with --full on the top level + the others under "also"')
     ap.add_argument('--batch', type=int, default=None, help='per-GPU batch override (asymptotic sweeps)')
     ap.add_argument('--layers', type=int, default=None, help='flow steps per level override (e.g. the reference default 32 for fpp_img)')
     ap.add_argument('--scaling', default='weak', choices=('weak', 'strong'),
                     help='weak (default): the per-GPU batch is fixed as N grows; strong: the GLOBAL batch is fixed (C4 512, C5 131072, ...), '
                          'per GPU = global / N')
     ap.add_argument('--no-graph', action='store_true', help='eager launches instead of hipGraph replay')
-    ap.add_argument('--skip-cpu', action='store_true', help='skip the CPU baseline leg')
+    ap.add_argument('--skip-cpu', action='store_true', help='skip the CPU baseline leg of --full')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: the other workloads, roofline, CPU baseline + step-1 parity, event-timed median, '
+                         'forward / inverse rates, detail file')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned (z, loss) as DIR/<name>.npy (float32; rows of z '
+                         'sampled at a fixed stride when z passes %d MB); the whole run uses the kernels\' ordered (deterministic) mode, '
+                         'so that two runs write the same arrays' % (DUMP_CAP_BYTES >> 20))
     ap.add_argument('--cpu-seconds', type=float, default=20.0)
     return ap.parse_args()
 
@@ -407,9 +418,21 @@ def resolve_batch(cfg, scaling, batch_override, world):
     return batch_override or cfg['batch'], cfg, strong
 
 
-def run_workload(name, args, pkg, rank, world, dev, steps, warmup, cpu_seconds):
-    """one workload: W warm-up steps, K timed steps (barrier + synchronize on both sides, max over ranks), then on rank 0
-    the dominant kernel's roofline, the CPU baseline and the step-1 parity; returns the JSON object (None off rank 0)."""
+def dump_outputs(out_dir, z, loss):
+    """what the last timed step returned, as float32 .npy files: z (its rows at a fixed stride when it passes DUMP_CAP_BYTES) and loss"""
+    os.makedirs(out_dir, exist_ok=True)
+    z = z.detach().float()
+    max_rows = max(1, DUMP_CAP_BYTES // (4 * max(1, z[0].numel())))
+    stride = max(1, -(-z.shape[0] // max_rows))
+    np.save(os.path.join(out_dir, 'z.npy'), z[::stride].cpu().numpy())
+    np.save(os.path.join(out_dir, 'loss.npy'), loss.detach().float().reshape(1).cpu().numpy())
+
+
+def run_workload(name, args, pkg, rank, world, dev, steps, warmup, cpu_seconds, dump_dir=None):
+    """one workload: W warm-up steps, K timed steps (barrier + synchronize on both sides, max over ranks), the outputs of the last one to
+    `dump_dir`; with --full then on rank 0 the event-timed steps, forward / inverse rates, the dominant kernel's roofline, the CPU
+    baseline and the step-1 parity.  Returns the JSON object (None off rank 0)."""
+    full = args.full
     nfdist = importlib.import_module(PKG + '.dist')
     nftrain = importlib.import_module(PKG + '.train')
     nfdata = importlib.import_module(PKG + '.data')
@@ -431,8 +454,9 @@ def run_workload(name, args, pkg, rank, world, dev, steps, warmup, cpu_seconds):
         y_cpu = y_cpu.reshape((B, ) + cfg['dims'])
     y = y_cpu.to(dev)                                        # resident in HBM before the timed region
 
-    z1, loss1 = trainer.train_on_batch(y)                    # step 1 (the parity object below compares THIS step with the CPU)
-    z1, loss1 = z1.detach().cpu().clone(), float(loss1)
+    z1, loss1 = trainer.train_on_batch(y)                    # step 1 (the parity object of --full compares THIS step with the CPU)
+    if full:
+        z1, loss1 = z1.detach().cpu().clone(), float(loss1)
     for _ in range(max(warmup, 4) - 1):                      # >= 4 so that graph capture happens before timing
         trainer.train_on_batch(y)
     torch.cuda.synchronize()
@@ -452,7 +476,26 @@ def run_workload(name, args, pkg, rank, world, dev, steps, warmup, cpu_seconds):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     loss_val = float(loss)
+    if dump_dir and rank == 0:
+        assert pkg._native.deterministic_timeouts() == 0, 'an ordered-mode turnstile wait gave up: the dumped outputs are invalid'
+        dump_outputs(dump_dir, z, loss)
+    timeouts = pkg._native.persistent_timeouts()
+    assert timeouts == 0, 'persistent kernels timed out %d times: the GPU was shared, results invalid' % timeouts
+    if full:
+        extra = measure_more(name, args, pkg, rank, world, dev, cfg, B, steps, trainer, net, y, y_cpu, state0, z1, loss1, cpu_seconds)
+    if rank != 0:
+        return None
+    out = headline_object(name, args, pkg, world, cfg, B, strong, steps, warmup, elapsed, loss_val, trainer, nftrain)
+    if full:
+        out.update(extra)
+    del trainer, net
+    torch.cuda.empty_cache()
+    return out
 
+
+def measure_more(name, args, pkg, rank, world, dev, cfg, B, steps, trainer, net, y, y_cpu, state0, z1, loss1, cpu_seconds):
+    """--full, after the timed steps of one workload: event-timed steps, forward / inverse rates, then on rank 0 the dominant kernel's
+    roofline, the CPU baseline and the step-1 parity (keys of the workload's JSON object; None off rank 0)"""
     # SURVEY 8(d): the MEDIAN of hipEvent-timed steps next to the wall-clock mean above -- the same K steps again, one event pair per
     # step on the launch stream (outside the contract's timed region, so that the event records cannot perturb `value`)
     stream = torch.cuda.current_stream()
@@ -484,7 +527,29 @@ def run_workload(name, args, pkg, rank, world, dev, steps, warmup, cpu_seconds):
     assert timeouts == 0, 'persistent kernels timed out %d times: the GPU was shared, results invalid' % timeouts
     if rank != 0:
         return None
-    roof = dominant_kernel_roofline(pkg, name, cfg, B, dev, trainer, y)
+    more = {'ms_per_step_event_median': round(ev_median, 4), 'ms_per_step_event_min': round(ev_min, 4),
+            'samples_per_s_event_median': round(B * world / (ev_median * 1e-3), 1),
+            'forward_samples_per_s': round(B * world / (fwd_ms * 1e-3), 1),
+            'inverse_samples_per_s': round(B * world / (inv_ms * 1e-3), 1),
+            'roofline': dominant_kernel_roofline(pkg, name, cfg, B, dev, trainer, y)}
+    if world == 1 and not args.skip_cpu:
+        more['cpu_baseline'], (zc, lc) = cpu_baseline(cfg, state0, y_cpu, cpu_seconds)
+        D = float(np.prod(cfg['dims']))
+        # the SAME first train step from the SAME initial weights and batch on both sides (forward incl. the data-dependent
+        # ActNorm initialisation); the full-size parity tests (tests/test_gpu_fullsize_parity.py) bound these differences by the
+        # distance of the fp32 CPU path from float64 arithmetic
+        more['parity'] = {'loss_gpu_step1': round(loss1, 6), 'loss_cpu_step1': round(lc, 6),
+                          'abs_dloss_per_dim': float('%.3e' % (abs(loss1 - lc) / D)),
+                          'max_abs_dz': float('%.3e' % float((z1 - zc).abs().max())),
+                          'max_abs_z': float('%.3e' % float(zc.abs().max())),
+                          'note': 'step 1 from identical initial weights and batch: GPU trainer vs the oracle on the host cores'}
+    else:
+        more['cpu_baseline'] = None
+    return more
+
+
+def headline_object(name, args, pkg, world, cfg, B, strong, steps, warmup, elapsed, loss_val, trainer, nftrain):
+    """the JSON object of one workload from its timed steps: samples/s, ms per step, loss, the whole-step counts against both roofs"""
     ms_step = 1e3 * elapsed / steps
     whole = None
     if cfg['datatype'] == 'image' and cfg['kind'] in ('glow', 'realnvp'):
@@ -523,9 +588,6 @@ def run_workload(name, args, pkg, rank, world, dev, steps, warmup, cpu_seconds):
         'steps': steps,
         'warmup': warmup,
         'ms_per_step': round(1e3 * elapsed / steps, 4),
-        'ms_per_step_event_median': round(ev_median, 4),
-        'ms_per_step_event_min': round(ev_min, 4),
-        'samples_per_s_event_median': round(B * world / (ev_median * 1e-3), 1),
         'higher_is_better': True,
         'scaling': 'strong' if strong else 'weak',
         'vs_baseline': None,
@@ -535,29 +597,11 @@ def run_workload(name, args, pkg, rank, world, dev, steps, warmup, cpu_seconds):
                    'scaling': 'strong (global batch fixed, per GPU = global / N)' if strong else 'weak (per-GPU batch fixed)', 'parallelism': 'dp%d' % world, 'hipgraph': trainer._g_fb is not None, 'deterministic': bool(pkg._native.deterministic()), 'dp_one_graph': bool(getattr(trainer, '_g_whole', False)) and trainer.bucket.collective, 'collective': collective_info(world)},
         'loss_nats': round(loss_val, 5),
         'bits_per_dim': round(nftrain.bits_per_dim(loss_val, cfg['dims']), 5),
-        'forward_samples_per_s': round(B * world / (fwd_ms * 1e-3), 1),
-        'inverse_samples_per_s': round(B * world / (inv_ms * 1e-3), 1),
         'grad_bucket_bytes': trainer.bucket.nbytes(),
-        'roofline': roof,
         'whole_step': whole,
     }
     if cfg['datatype'] == 'image':
         out['bits_per_dim_plus_log2_255'] = round(out['bits_per_dim'] + math.log2(255.0), 5)
-    if world == 1 and not args.skip_cpu:
-        out['cpu_baseline'], (zc, lc) = cpu_baseline(cfg, state0, y_cpu, cpu_seconds)
-        D = float(np.prod(cfg['dims']))
-        # the SAME first train step from the SAME initial weights and batch on both sides (forward incl. the data-dependent
-        # ActNorm initialisation); the full-size parity tests (tests/test_gpu_fullsize_parity.py) bound these differences by the
-        # distance of the fp32 CPU path from float64 arithmetic
-        out['parity'] = {'loss_gpu_step1': round(loss1, 6), 'loss_cpu_step1': round(lc, 6),
-                         'abs_dloss_per_dim': float('%.3e' % (abs(loss1 - lc) / D)),
-                         'max_abs_dz': float('%.3e' % float((z1 - zc).abs().max())),
-                         'max_abs_z': float('%.3e' % float(zc.abs().max())),
-                         'note': 'step 1 from identical initial weights and batch: GPU trainer vs the oracle on the host cores'}
-    else:
-        out['cpu_baseline'] = None
-    del trainer, net
-    torch.cuda.empty_cache()
     return out
 
 
@@ -649,8 +693,10 @@ def collective_info(world):
 
 
 def self_spawn(args):
-    """`python bench.py --gpus N` outside torchrun: re-exec under torch.distributed.run with N ranks on this node."""
+    """`python bench.py --gpus N` outside torchrun: the same command under torch.distributed.run with N ranks on this node, in a child
+    process (this one has already opened the GPU); returns its exit status."""
     import socket
+    import subprocess
     n_dev = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if n_dev < args.gpus:
         raise SystemExit('bench.py --gpus %d: this node exposes %d GPU(s); the bench measures the MI355X path only '
@@ -662,7 +708,7 @@ def self_spawn(args):
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')        # the host driver only supports dmabuf IPC (RCCL needs it)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(args.gpus), '--master-addr',
            '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execve(sys.executable, cmd, env)
+    return subprocess.run(cmd, env=env).returncode
 
 
 def _claim_stdout():
@@ -689,7 +735,7 @@ def _emit_line(fd, line):
 def main():
     args = parse()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
-        self_spawn(args)                                     # does not return
+        sys.exit(self_spawn(args))
     json_fd = _claim_stdout()
     pkg = importlib.import_module(PKG)
     nfdist = importlib.import_module(PKG + '.dist')
@@ -699,12 +745,18 @@ def main():
     assert torch.cuda.is_available(), 'bench.py measures the MI355X path; no GPU visible'
     torch.cuda.set_device(local_rank)                        # BEFORE the library is loaded / armed: one device per process
     pkg._native.load()
+    if args.dump_outputs:
+        # the default mode adds some batch sums (log-dets, channel statistics, weight gradients) by float atomics in arrival order: two
+        # runs from identical inputs differ in the last bits at step 1, and Adam turns that into different weights, z and loss a few
+        # steps later (C4: max |dz| ~ 5 by step 3).  The ordered mode adds them in a fixed order, every step bit-identical run to run;
+        # it is slower (C4 about 1.15 x), so only the runs that write outputs use it, and the line's config says so
+        pkg._native.deterministic(True)
     dev = torch.device('cuda', local_rank)
-    # BASELINE.json quotes the metric on RealNVP moons-2D (c1) and Glow CIFAR-10 (c4): the default run measures both -- the
-    # line's top level is c4 (the larger one), c1 rides along as a second object of the same shape under "also"
+    # BASELINE.json quotes the metric on RealNVP moons-2D (c1) and Glow CIFAR-10 (c4): the line's top level is c4 (the larger one); with
+    # --full c1 and the other workloads ride along as objects of the same shape under "also"
     primary = args.config or 'c4'
-    out = run_workload(primary, args, pkg, rank, world, dev, args.steps, args.warmup, args.cpu_seconds)
-    if args.config is None and args.batch is None and args.layers is None:
+    out = run_workload(primary, args, pkg, rank, world, dev, args.steps, args.warmup, args.cpu_seconds, args.dump_outputs)
+    if args.full and args.config is None and args.batch is None and args.layers is None:
         # (200 steps for the configs whose step is 0.7 - 2.5 ms: a 50-step region is 35 - 125 ms, where one host or clock hiccup moves the
         #  mean by several per cent -- wall-clock means of 1.36 .. 1.51 ms were seen for C1 next to an event median of 1.31)
         also = run_workload('c1', args, pkg, rank, world, dev, max(args.steps, 200), args.warmup, min(args.cpu_seconds, 6.0))
@@ -731,8 +783,10 @@ def main():
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
     if rank == 0:
-        detail = write_detail(out)
-        sys.stderr.write('bench detail (every workload, full notes):\n' + json.dumps(out) + '\n')
+        detail = None
+        if args.full:
+            detail = write_detail(out)
+            sys.stderr.write('bench detail (every workload, full notes):\n' + json.dumps(out) + '\n')
         _emit_line(json_fd, headline_of(out, detail))
 
 

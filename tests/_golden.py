@@ -26,6 +26,30 @@ def group(name, prefix, device='cpu'):
     return out
 
 
+def captures(name, prefix, device='cpu'):
+    """``group`` of every capture of ``name``: the committed one and, where ``name``.alt.npz exists, the same reference run on a host
+    CPU whose math library rounds differently (make_goldens.py --alt: only the arrays that differ, laid over the committed ones)."""
+    out = [group(name, prefix, device)]
+    if os.path.exists(os.path.join(GOLDEN_DIR, name + '.alt.npz')):
+        alt = {k[len(prefix):]: torch.from_numpy(v.copy()).to(device) for k, v in _load(name + '.alt').items() if k.startswith(prefix)}
+        if alt:
+            out.append(dict(group(name, prefix, device), **alt))
+    return out
+
+
+def matches_a_capture(check, caps):
+    """``check(g)`` must pass against ONE capture in full (every assertion against the same one); the first capture's failure is
+    what is reported when none matches."""
+    first = None
+    for g in caps:
+        try:
+            check(g)
+            return
+        except AssertionError as e:
+            first = first or e
+    raise first
+
+
 def keys(name):
     return list(_load(name).keys())
 

@@ -13,6 +13,7 @@ Files (np.savez_compressed, all fp32 unless integer):
   model_<name>.npz G9  small end-to-end models: initial state_dict, input, (z, ld) train+eval, loss, all grads,
                         mutated state, inverse
   mainloop_<name>.npz G11 main.py's train_on_batch (Adam + StepLR) for 3 steps: per-step batch, z, loss; final state_dict
+  <name>.alt.npz  the arrays of ops / model_maf2d that a second host CPU computes differently (--alt, see write_alt)
 """
 import importlib
 import os
@@ -24,6 +25,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
+OUT = HERE                  # where the make_* functions write (a scratch directory under --alt)
 sys.path.insert(0, ROOT)
 sys.dont_write_bytecode = True
 
@@ -73,7 +75,7 @@ def make_indexmaps():
             out['1d/%d/odd%d/z0' % (D, odd)] = npy(z0).astype(np.int32)
             out['1d/%d/odd%d/z1' % (D, odd)] = npy(z1).astype(np.int32)
             assert torch.equal(rsq.unsqueeze1d(z0, z1, odd), z)
-    np.savez_compressed(os.path.join(HERE, 'indexmaps.npz'), **out)
+    np.savez_compressed(os.path.join(OUT, 'indexmaps.npz'), **out)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -298,7 +300,7 @@ def make_ops():
                      ('ld_eval', lde), ('x_inv', xi), ('ld_inv', ldi)]:
             out[k + n] = npy(v)
 
-    np.savez_compressed(os.path.join(HERE, 'ops.npz'), **out)
+    np.savez_compressed(os.path.join(OUT, 'ops.npz'), **out)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -358,7 +360,7 @@ def make_models(only=None):
             ze, lde = net(y.clone())
             xe, ldie = net.backward(ze.clone())
             out['eval/z'], out['eval/ld'], out['eval/x_inv'], out['eval/ld_inv'] = npy(ze), npy(lde), npy(xe), npy(ldie)
-        np.savez_compressed(os.path.join(HERE, 'model_%s.npz' % name), **out)
+        np.savez_compressed(os.path.join(OUT, 'model_%s.npz' % name), **out)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -396,13 +398,35 @@ def make_mainloop():
             out['step%d/y' % s], out['step%d/z' % s], out['step%d/loss' % s] = npy(y), npy(z), npy(loss)
         for k, v in net.state_dict().items():
             out['sdN/' + k] = npy(v)
-        np.savez_compressed(os.path.join(HERE, 'mainloop_%s.npz' % name), **out)
+        np.savez_compressed(os.path.join(OUT, 'mainloop_%s.npz' % name), **out)
+
+
+def write_alt(names):
+    """<name>.alt.npz for each of ``names`` ('ops', 'model_<case>'): the arrays of a fresh capture on THIS host that differ from the
+    committed <name>.npz.  The reference's own results move in the last bits with the host CPU's math library (LAPACK, vector
+    exp / log), and the bit-exact or 1e-5 checks of tests/test_oracle_golden.py cannot hold across hosts; tests/_golden.captures
+    overlays the alt arrays on the committed capture, and a check passes when the oracle matches one capture in full."""
+    import tempfile
+    global OUT
+    OUT = tempfile.mkdtemp()
+    if 'ops' in names:
+        make_ops()
+    models = {n[len('model_'):] for n in names if n.startswith('model_')}
+    if models:
+        make_models(models)
+    for name in names:
+        with np.load(os.path.join(HERE, name + '.npz')) as a, np.load(os.path.join(OUT, name + '.npz')) as b:
+            alt = {k: b[k] for k in b.files if k not in a.files or not np.array_equal(a[k], b[k], equal_nan=True)}
+        np.savez_compressed(os.path.join(HERE, name + '.alt.npz'), **alt)
+        print('%s.alt.npz: %d of the arrays differ' % (name, len(alt)))
 
 
 if __name__ == '__main__':
     import warnings
     warnings.filterwarnings('ignore')
-    if sys.argv[1:] == ['mainloop']:
+    if sys.argv[1:2] == ['--alt']:                                  # python make_goldens.py --alt ops model_maf2d
+        write_alt(sys.argv[2:])
+    elif sys.argv[1:] == ['mainloop']:
         make_mainloop()
     elif len(sys.argv) > 1:                                        # python make_goldens.py realnvp_img flowpp_img: only these models
         make_models(set(sys.argv[1:]))

@@ -306,6 +306,27 @@ def test_bench_headline_stays_short_and_parses():
         bench.headline_of(fat)
 
 
+def test_bench_dump_outputs_are_float32_and_capped(tmp_path):
+    """bench.py --dump-outputs: z and loss of the last timed step as float32 .npy files; a z past DUMP_CAP_BYTES keeps its rows at a
+    fixed stride (the same rows on every run), so that the files stay small enough to compare two builds output for output."""
+    import importlib.util
+    import os
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench', os.path.join(ROOT, 'bench.py'))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert b.DUMP_CAP_BYTES < 64 << 20
+    z = torch.arange(1000 * 3, dtype=torch.float64).reshape(1000, 3)
+    b.dump_outputs(str(tmp_path / 'all'), z, torch.tensor(1.5))
+    got = np.load(str(tmp_path / 'all' / 'z.npy'))
+    assert got.dtype == np.float32 and np.array_equal(got, z.float().numpy())
+    loss = np.load(str(tmp_path / 'all' / 'loss.npy'))
+    assert loss.dtype == np.float32 and loss.tolist() == [1.5]
+    b.DUMP_CAP_BYTES = 1000                                   # 12 000 bytes of z, 83 rows fit: every 13th row
+    b.dump_outputs(str(tmp_path / 'cut'), z, torch.tensor(1.5))
+    got = np.load(str(tmp_path / 'cut' / 'z.npy'))
+    assert got.nbytes <= 1000 and np.array_equal(got, z[::13].float().numpy())
+
 def test_bench_scaling_modes_resolve_the_per_gpu_batch():
     """bench.py --scaling: weak keeps the per-GPU batch whatever N is, strong keeps the GLOBAL batch (C4: the literal 512 of BASELINE.json,
     C5: 131072) and gives every rank global / N rows; both report what they did in the config object."""

@@ -140,7 +140,10 @@ def test_logit(eps):
 
 @pytest.mark.parametrize('tag', ['K4_2d', 'K8_2d', 'K4_4d'])
 def test_mixlogcdf(tag):
-    g = G.group('ops', 'mixlogcdf/%s/' % tag)
+    G.matches_a_capture(_mixlogcdf_against, G.captures('ops', 'mixlogcdf/%s/' % tag))
+
+
+def _mixlogcdf_against(g):
     x, lp = g['x'].requires_grad_(True), g['logpi_raw'].requires_grad_(True)
     mu, s = g['mu'].requires_grad_(True), g['s'].requires_grad_(True)
     logpi = torch.log_softmax(lp, dim=1)
@@ -195,7 +198,10 @@ class _FixedMasks:
 
 @pytest.mark.parametrize('D', [2, 5])
 def test_ar_transform(D):
-    g = G.group('ops', 'ar/%d/' % D)
+    G.matches_a_capture(lambda g: _ar_transform_against(g, D), G.captures('ops', 'ar/%d/' % D))
+
+
+def _ar_transform_against(g, D):
     sd = {k[len('sd/'):]: v.clone() for k, v in g.items() if k.startswith('sd/')}
     layer_plan = dict(op='ar', prefix='', dims=(D, ))
     ora = om.FlowOracle('maf', (D, ), None, 0, sd, training=True)
@@ -235,9 +241,12 @@ def test_ar_transform(D):
 
 @pytest.mark.parametrize('name', list(G.MODEL_CASES))
 def test_models(name):
+    G.matches_a_capture(lambda g: _model_against(g, name), G.captures('model_' + name, ''))
+
+
+def _model_against(g, name):
     kind, _, dims, datatype, layers, mix = G.MODEL_CASES[name]
-    sd = G.group('model_' + name, 'sd0/')
-    g = G.group('model_' + name, '')
+    sd = {k[len('sd0/'):]: v.clone() for k, v in g.items() if k.startswith('sd0/')}
     ora = om.FlowOracle(kind, dims, datatype, layers, sd, mixtures=mix, training=True, logdet='exact', spnorm_coeff=0.9)
     ora.requires_grad_(True)
     G.seed_noise(777)
@@ -254,7 +263,7 @@ def test_models(name):
             G.assert_close(v.grad, want, 2 * TOL * max(1.0, float(want.abs().max())), what=k)
             n += 1
     assert n > 4
-    for k, want in G.group('model_' + name, 'sd1/').items():
+    for k, want in ((k[len('sd1/'):], v) for k, v in g.items() if k.startswith('sd1/')):
         G.assert_close(sd[k].detach().float(), want.float(), 1e-6, what=k)
     ora.requires_grad_(False)
     tol_inv = 2e-4 if kind == 'flowpp' else TOL

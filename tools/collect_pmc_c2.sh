@@ -17,5 +17,5 @@ rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_c2 -o st -- pyth
 F=$(find /tmp/ks_c2 -name "st_kernel_stats.csv" | head -1)
 [ -n "$F" ] && head -40 $F > $OUT/${R}_c2_kernel_stats.csv
 cd $GRAFT_REPO_ROOT
-python bench.py --config c2 --steps 200 --cpu-seconds 15 > $OUT/${R}_bench_c2.json 2> /dev/null
-python bench.py > $OUT/${R}_bench_default.json 2> $OUT/bench_default.err
+python bench.py --full --config c2 --steps 200 --cpu-seconds 15 > $OUT/${R}_bench_c2.json 2> /dev/null
+python bench.py --full > $OUT/${R}_bench_default.json 2> $OUT/bench_default.err

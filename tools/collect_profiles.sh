@@ -28,14 +28,14 @@ rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_f -o st -- pytho
 F=$(find /tmp/ks_f -name "st_kernel_stats.csv" | head -1)
 [ -n "$F" ] && head -45 $F > $OUT/${R}_fpp_img_kernel_stats.csv
 cd $GRAFT_REPO_ROOT
-python bench.py --config fpp_img --steps 50 --cpu-seconds 15 > $OUT/${R}_bench_fpp_img.json 2> /dev/null
+python bench.py --full --config fpp_img --steps 50 --cpu-seconds 15 > $OUT/${R}_bench_fpp_img.json 2> /dev/null
 python tools/probes/flowpp_img_kernels.py 64 > $OUT/${R}_fpp_img_launch_times.txt 2>&1
 python tools/probes/flowpp_img_step.py 2 64 10 > $OUT/${R}_fpp_img_step.txt 2>&1
 python tools/kernel_sweep.py > $OUT/${R}_kernel_sweep.txt 2> $OUT/sweep.err
 for c in c1 c2 c3 c4 c5 rnvp_img; do
-  python bench.py --config $c --steps 50 --cpu-seconds 15 > $OUT/${R}_bench_$c.json 2> /dev/null
+  python bench.py --full --config $c --steps 50 --cpu-seconds 15 > $OUT/${R}_bench_$c.json 2> /dev/null
 done
-python bench.py > $OUT/${R}_bench_default.json 2> $OUT/bench_default.err
+python bench.py --full > $OUT/${R}_bench_default.json 2> $OUT/bench_default.err
 # per-step launch census of the two metric configs (steady-state window between marker launches) and per-grid chain launch times
 cd /tmp
 for c in c4 c1 fpp_img rnvp_img; do
@@ -73,7 +73,7 @@ SECONDS_PER=4 python tools/cpu_threads.py c1 1 4 8 16 32 >> $OUT/${R}_cpu_thread
 # all-reduce + graph B, or -- NF_DP_ONE_GRAPH=1 -- the all-reduce captured inside the step graph) against the plain single-process step
 for c in c4 c1 c5; do for m in "NF_DP_FORCE_COLLECTIVE=0" "NF_DP_FORCE_COLLECTIVE=1" "NF_DP_FORCE_COLLECTIVE=1 NF_DP_ONE_GRAPH=1"; do
   echo "== $c $m" >> $OUT/${R}_dp_one_rank.txt
-  env $m python bench.py --config $c --skip-cpu --steps 50 2> /dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('samples/s', d['value'], 'ms/step', d['ms_per_step'], 'event median', d.get('ms_per_step_event_median'), 'one_graph', d['config'].get('dp_one_graph'), d['config'].get('collective'))" >> $OUT/${R}_dp_one_rank.txt 2>&1
+  env $m python bench.py --full --config $c --skip-cpu --steps 50 2> /dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('samples/s', d['value'], 'ms/step', d['ms_per_step'], 'event median', d.get('ms_per_step_event_median'), 'one_graph', d['config'].get('dp_one_graph'), d['config'].get('collective'))" >> $OUT/${R}_dp_one_rank.txt 2>&1
 done; done
 # issue rate of the transcendental VALU instructions (the roof quoted for the mixture-of-logistics kernels)
 hipcc --offload-arch=gfx950 -O3 -o /tmp/vexp_rate_probe tools/probes/vexp_rate_probe.hip 2> /dev/null && /tmp/vexp_rate_probe > $OUT/${R}_vexp_rate.txt 2>&1

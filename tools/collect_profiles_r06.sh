@@ -26,9 +26,9 @@ cp $OUT/${R}_cpu_threads.txt $GRAFT_REPO_ROOT/profiles/${R}_cpu_threads.txt
 python tools/kernel_sweep.py > $OUT/${R}_kernel_sweep.txt 2> $OUT/sweep.err
 python tools/model_sweep.py > $OUT/${R}_model_sweep.txt 2> $OUT/model_sweep.err
 for c in c1 c2 c3 c4 c5 rnvp_img fpp_img; do
-  python bench.py --config $c --steps 50 --cpu-seconds 15 > $OUT/${R}_bench_$c.json 2> /dev/null
+  python bench.py --full --config $c --steps 50 --cpu-seconds 15 > $OUT/${R}_bench_$c.json 2> /dev/null
 done
-python bench.py > $OUT/${R}_bench_default.json 2> $OUT/bench_default.err
+python bench.py --full > $OUT/${R}_bench_default.json 2> $OUT/bench_default.err
 cp gpurun_out/bench_detail.json $OUT/${R}_bench_detail.json
 # per-step launch census (steady-state window between marker launches) and per-grid chain launch times
 cd /tmp

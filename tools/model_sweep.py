@@ -19,7 +19,7 @@ if '--big' in sys.argv:
 print('%-6s %10s %14s %12s %10s %10s   %s' % ('config', 'batch', 'samples/s', 'ms/step', 'mfma', 'hbm', 'dominant kernel (us per launch)'))
 for cfg, B, steps in RUNS:
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--config', cfg, '--batch', str(B), '--steps', str(steps), '--warmup', '2',
-                        '--skip-cpu'], capture_output=True, text=True, timeout=1500)
+                        '--full', '--skip-cpu'], capture_output=True, text=True, timeout=1500)
     line = [l for l in r.stdout.splitlines() if l.startswith('{')]
     if r.returncode != 0 or not line:
         print('%-6s %10d   failed: %s' % (cfg, B, (r.stderr.strip().splitlines() or ['?'])[-1][:120]))
