@@ -343,6 +343,22 @@ __device__ __forceinline__ int nf_cc_valid_px(int64_t Npx, int64_t first, int co
 // one value left.  Pixels beyond the batch come in whole samples, i.e. whole 16-lane groups (a map has >= 16 pixels), and hold
 // zeros: inside a group the rule above is exact as it stands; at mask 16 an empty group is skipped (lo_ok / hi_ok).
 // Result: lane c32 holds S and M2 of value index `which` (a function of its low bits) over the half's valid pixels.
+// The partner's value at lane mask m (m a compile-time constant once the butterflies are unrolled), without the LDS round trip of
+// ds_bpermute (__shfl_xor) where the lane pairing allows: DPP quad_perm for m = 1, 2 and row_ror:8 for m = 8 (a rotation by half a
+// 16-lane row IS the xor), ds_swizzle bitmask mode (and 31, xor m: no address operand) for m = 4, 16.  Same pairing as __shfl_xor,
+// so the same values and the same sums bit for bit.  (The OWN = 2 butterflies keep __shfl_xor: there this form cost the 8 x 8
+// kernels 8 - 12 bytes of scratch per lane.)
+__device__ __forceinline__ float nf_cc_xor(float v, int m) {
+    const int x = __float_as_int(v);
+    switch (m) {
+        case 1: return __int_as_float(__builtin_amdgcn_mov_dpp(x, 0xB1, 0xF, 0xF, true));     // quad_perm [1, 0, 3, 2]
+        case 2: return __int_as_float(__builtin_amdgcn_mov_dpp(x, 0x4E, 0xF, 0xF, true));     // quad_perm [2, 3, 0, 1]
+        case 4: return __int_as_float(__builtin_amdgcn_ds_swizzle(x, 0x101F));
+        case 8: return __int_as_float(__builtin_amdgcn_mov_dpp(x, 0x128, 0xF, 0xF, true));    // row_ror:8
+        case 16: return __int_as_float(__builtin_amdgcn_ds_swizzle(x, 0x401F));
+        default: return __shfl_xor(v, m, NF_WAVE);
+    }
+}
 __device__ __forceinline__ void nf_cc_merge(float& S, float& M2, float So, float Mo, float half_inv_m) {
     const float dl = So - S;
     M2 = (M2 + Mo) + dl * dl * half_inv_m;
@@ -355,8 +371,8 @@ __device__ __forceinline__ void nf_cc_half_stats(const float (&v)[OWN], bool lo_
     if constexpr (OWN == 1) {                           // whole merges only
         S = v[0];
         M2 = 0.f;
-        for (int m = 1; m < 16; m *= 2) nf_cc_merge(S, M2, __shfl_xor(S, m, NF_WAVE), __shfl_xor(M2, m, NF_WAVE), 0.5f / (float)m);
-        const float So = __shfl_xor(S, 16, NF_WAVE), Mo = __shfl_xor(M2, 16, NF_WAVE);
+        for (int m = 1; m < 16; m *= 2) nf_cc_merge(S, M2, nf_cc_xor(S, m), nf_cc_xor(M2, m), 0.5f / (float)m);
+        const float So = nf_cc_xor(S, 16), Mo = nf_cc_xor(M2, 16);
         const bool me_ok = (c32 & 16) ? hi_ok : lo_ok, ot_ok = (c32 & 16) ? lo_ok : hi_ok;
         if (me_ok && ot_ok) nf_cc_merge(S, M2, So, Mo, 0.5f / 16.f);
         else if (ot_ok) { S = So; M2 = Mo; }
@@ -384,7 +400,7 @@ __device__ __forceinline__ void nf_cc_half_stats(const float (&v)[OWN], bool lo_
         for (int k = 0; k < 4; ++k) {
             const float keep = up ? v[k + 4] : v[k], send = up ? v[k] : v[k + 4];
             s4[k] = keep; q4[k] = 0.f;
-            nf_cc_merge(s4[k], q4[k], __shfl_xor(send, 1, NF_WAVE), 0.f, 0.5f);
+            nf_cc_merge(s4[k], q4[k], nf_cc_xor(send, 1), 0.f, 0.5f);
         }
         w = up ? 4 : 0;
         m = 2;
@@ -400,8 +416,8 @@ __device__ __forceinline__ void nf_cc_half_stats(const float (&v)[OWN], bool lo_
             const float ks = up ? s4[k + 2] : s4[k], ss = up ? s4[k] : s4[k + 2];
             const float kq_ = up ? q4[k + 2] : q4[k], sq = up ? q4[k] : q4[k + 2];
             s2[k] = ks; q2[k] = kq_;
-            const float os = __shfl_xor(ss, m, NF_WAVE);
-            const float oq = OWN == 8 ? __shfl_xor(sq, m, NF_WAVE) : 0.f;      // OWN = 4: first merge, the partner's M2 is zero
+            const float os = nf_cc_xor(ss, m);
+            const float oq = OWN == 8 ? nf_cc_xor(sq, m) : 0.f;      // OWN = 4: first merge, the partner's M2 is zero
             nf_cc_merge(s2[k], q2[k], os, oq, 0.5f / (float)m);
         }
         w += up ? 2 : 0;
@@ -412,13 +428,13 @@ __device__ __forceinline__ void nf_cc_half_stats(const float (&v)[OWN], bool lo_
         const float ks = up ? s2[1] : s2[0], ss = up ? s2[0] : s2[1];
         const float kq_ = up ? q2[1] : q2[0], sq = up ? q2[0] : q2[1];
         S = ks; M2 = kq_;
-        nf_cc_merge(S, M2, __shfl_xor(ss, m, NF_WAVE), __shfl_xor(sq, m, NF_WAVE), 0.5f / (float)m);
+        nf_cc_merge(S, M2, nf_cc_xor(ss, m), nf_cc_xor(sq, m), 0.5f / (float)m);
         w += up ? 1 : 0;
         m *= 2;
     }
-    for (; m < 16; m *= 2) nf_cc_merge(S, M2, __shfl_xor(S, m, NF_WAVE), __shfl_xor(M2, m, NF_WAVE), 0.5f / (float)m);
+    for (; m < 16; m *= 2) nf_cc_merge(S, M2, nf_cc_xor(S, m), nf_cc_xor(M2, m), 0.5f / (float)m);
     {   // the two 16-lane groups: either may be empty (beyond the batch)
-        const float So = __shfl_xor(S, 16, NF_WAVE), Mo = __shfl_xor(M2, 16, NF_WAVE);
+        const float So = nf_cc_xor(S, 16), Mo = nf_cc_xor(M2, 16);
         const bool me_ok = (c32 & 16) ? hi_ok : lo_ok, ot_ok = (c32 & 16) ? lo_ok : hi_ok;
         if (me_ok && ot_ok) nf_cc_merge(S, M2, So, Mo, 0.5f / 16.f);
         else if (ot_ok) { S = So; M2 = Mo; }
@@ -457,7 +473,7 @@ __device__ __forceinline__ void nf_cc_collect_slots(float* xs, const unsigned lo
 
 __device__ __forceinline__ float nf_cc_sum32(float v) {      // over the 32 lanes of a wave half, fixed order
 #pragma unroll
-    for (int off = 1; off < 32; off <<= 1) v += __shfl_xor(v, off, NF_WAVE);
+    for (int off = 1; off < 32; off <<= 1) v += nf_cc_xor(v, off);
     return v;
 }
 
@@ -493,10 +509,11 @@ __device__ __forceinline__ void nf_cc_merge_rows(const float* xs, int XS, int n,
 }
 
 // Returns true in the ONE lane per channel that holds the channel's totals (ci, S, M2) -- the caller finishes the BatchNorm constants
-// there and then synchronises: no barrier between the merge and the constants.
-template <int NPB>
+// there and then synchronises: no barrier between the merge and the constants.  peek() runs once every row has arrived (the halo's
+// early loads).
+template <int NPB, typename Peek>
 __device__ __forceinline__ bool nf_cc_stats_exchange(float* sm, const NfCcLds& L, unsigned long long* slots, unsigned gbase, int round,
-                                                     int64_t Npx, int PXW, int& ci_out, float& S_out, float& M2_out) {
+                                                     int64_t Npx, int PXW, int& ci_out, float& S_out, float& M2_out, Peek&& peek) {
     float* red = sm + L.RED;
     float* xs = sm + L.RS;
     float* tot = sm + L.TOT;
@@ -536,7 +553,10 @@ __device__ __forceinline__ bool nf_cc_stats_exchange(float* sm, const NfCcLds& L
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
-    if (G == 1) return threadIdx.x < 32;
+    if (G == 1) {
+        peek();
+        return threadIdx.x < 32;
+    }
     const unsigned long long* rs = slots + (size_t)round * NF_CC_MAX_BLOCKS * 64;
     const unsigned gen = gbase + (unsigned)(round + 1);
     if (round == 1) NF_CC_STAMP(57);
@@ -550,6 +570,7 @@ __device__ __forceinline__ bool nf_cc_stats_exchange(float* sm, const NfCcLds& L
         // every workgroup polls every row: thread (wave w, half h, lane l) reduces channel ci = 2 w + h over the workgroups b = l,
         // l + 32, ... in a fixed order, then a butterfly over the 32 lanes
         nf_cc_collect_slots(xs, rs, gen, G, XS);
+        peek();
         if (round == 1) NF_CC_STAMP(58);
         __syncthreads();
         if (round == 1) NF_CC_STAMP(59);
@@ -575,6 +596,7 @@ __device__ __forceinline__ bool nf_cc_stats_exchange(float* sm, const NfCcLds& L
             __syncthreads();                            // the group's rows are read before the gather buffer is reused
         }
         nf_cc_collect_slots(xs, gs, gen, NG, XS);
+        peek();
         if (round == 1) NF_CC_STAMP(58);
         __syncthreads();
         if (round == 1) NF_CC_STAMP(59);
@@ -621,23 +643,37 @@ __device__ __forceinline__ void nf_cc_halo_publish(unsigned long long* hslots, u
         __hip_atomic_store(base + c * g.W, gen | (unsigned long long)__float_as_uint(v[rr]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
-// thread t < 32 W: channel t / W, column t % W of BOTH halo rows (s = 0, 1; an image border has none).  Returns the frame position of
-// the value this call delivers in `v`, or -1; call once per row s.
+// thread t < 32 W: channel t / W, column t % W of BOTH halo rows (s = 0, 1; an image border has none).
+__device__ __forceinline__ const unsigned long long* nf_cc_halo_slot(const unsigned long long* hslots, int layer, const NfCvGeo& g, int tile,
+                                                                     int s) {
+    return hslots + ((size_t)layer * NF_CC_MAX_BLOCKS + tile) * NF_CC_HALO_SLOTS(g.W) + s * 32 * g.W + threadIdx.x;
+}
+// The first look at both slots, issued early: inside the layer's grid exchange, once every workgroup's statistics have arrived (a
+// neighbour publishes its rows before its statistics, so they are there too, as a rule).  The round trip then runs under the merge,
+// the constants and the normalise of our own pixels instead of in front of the frame stores (0.6 us per 16 x 16 layer).
+__device__ __forceinline__ void nf_cc_halo_peek(unsigned long long (&w)[2], const unsigned long long* hslots, int layer, const NfCvGeo& g,
+                                                int tile, int y0) {
+    if (threadIdx.x < 32 * g.W) {
+        if (y0 > 0) w[0] = __hip_atomic_load(nf_cc_halo_slot(hslots, layer, g, tile, 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (y0 + g.TH < g.H) w[1] = __hip_atomic_load(nf_cc_halo_slot(hslots, layer, g, tile, 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// Returns the frame position of the value this call delivers in `v`, or -1; call once per row s.  w0: what nf_cc_halo_peek saw (0: no
+// peek); polled again until the generation matches.
 __device__ __forceinline__ int nf_cc_halo_poll(const unsigned long long* hslots, unsigned gbase, int layer, const NfCvGeo& g, int tile, int y0,
-                                               int s, float& v) {
+                                               int s, float& v, unsigned long long w0 = 0) {
     const bool has = s == 0 ? y0 > 0 : y0 + g.TH < g.H;
     if (!has) return -1;
-    const int t = threadIdx.x, x = t & (g.W - 1);
-    const unsigned long long* p = hslots + ((size_t)layer * NF_CC_MAX_BLOCKS + tile) * NF_CC_HALO_SLOTS(g.W) + s * 32 * g.W + t;
+    const int x = threadIdx.x & (g.W - 1);
+    const unsigned long long* p = nf_cc_halo_slot(hslots, layer, g, tile, s);
     const unsigned gen = gbase + (unsigned)(layer + 1);
-    unsigned long long w;
+    unsigned long long w = w0;
     unsigned spins = 0;
-    do {
-        w = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((unsigned)(w >> 32) == gen) break;
+    while ((unsigned)(w >> 32) != gen) {
         if (++spins > nf_cc_spin_limit) { NF_PERSIST_GIVE_UP(nf_cc); break; }
-        __builtin_amdgcn_s_sleep(1);
-    } while (true);
+        if (spins > 1) __builtin_amdgcn_s_sleep(1);
+        w = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     v = __uint_as_float((unsigned)w);
     return (s == 0 ? 0 : (g.TH + 1) * g.FW) + x + 1;             // frame row 0 / TH + 1, column x + halo
 }
@@ -1294,10 +1330,13 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_
         }
         if (halo) nf_cc_halo_publish<OWN>(hslots, gbase, l, g, (int)tile, y0, px, kq, hs, own);
         NF_CC_STAMP(4 + 8 * l);
+        unsigned long long hw[2] = {0ull, 0ull};        // the neighbours' boundary rows as first seen (nf_cc_halo_peek)
         if (training) {
             int k;
             float tS, tM2;
-            const bool fin = nf_cc_stats_exchange<NPB>(sm, L, slots, gbase, l, Npx, PXW, k, tS, tM2);
+            const bool fin = nf_cc_stats_exchange<NPB>(sm, L, slots, gbase, l, Npx, PXW, k, tS, tM2, [&] {
+                if (halo) nf_cc_halo_peek(hw, hslots, l, g, (int)tile, y0);
+            });
             NF_CC_STAMP(5 + 8 * l);
             if (fin) {                                  // the lane that holds channel k's totals finishes its constants
                 const float invN = 1.f / (float)Npx;
@@ -1332,17 +1371,8 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_
         }
         __syncthreads();
         NF_CC_STAMP(6 + 8 * l);
-        if (halo && threadIdx.x < 32 * g.W) {           // the neighbours' boundary rows, normalised like our own pixels
-            const int c = threadIdx.x >> g.lgW;
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                float v = 0.f;
-                const int f = nf_cc_halo_poll(hslots, gbase, l, g, (int)tile, y0, s2, v);
-                if (f >= 0) nf_cc_frame_store1(Fr, CSr, c, f, fmaxf(fmaf(v, kc[c], kc[32 + c]), 0.f));
-            }
-        }
         // normalise + ReLU back into the frame, split into the three bf16 planes (a lane's values are whole channel quads: one 8-byte
-        // store per plane); next weights into Wl
+        // store per plane); then the halo rows, whose loads were issued inside the exchange; next weights into Wl
 #pragma unroll
         for (int j = 0; j < OWN / 4; ++j) {
             const int c0 = nf_cv_cd_row(OWN * kq + 4 * j, hs);          // channels c0 .. c0 + 3
@@ -1361,6 +1391,15 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_
             const int c0 = nf_cv_cd_row(OWN * kq, hs);                  // channels c0, c0 + 1
             nf_cc_frame_store2(Fr, CSr, c0, fpos, pv ? fmaxf(fmaf(own[0], kc[c0], kc[32 + c0]), 0.f) : 0.f,
                                pv ? fmaxf(fmaf(own[1], kc[c0 + 1], kc[32 + c0 + 1]), 0.f) : 0.f);
+        }
+        if (halo && threadIdx.x < 32 * g.W) {           // the neighbours' boundary rows, normalised like our own pixels
+            const int c = threadIdx.x >> g.lgW;
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                float v = 0.f;
+                const int f = nf_cc_halo_poll(hslots, gbase, l, g, (int)tile, y0, s2, v, hw[s2]);
+                if (f >= 0) nf_cc_frame_store1(Fr, CSr, c, f, fmaxf(fmaf(v, kc[c], kc[32 + c]), 0.f));
+            }
         }
         if (l < NF_CC_NB - 1) {
             if (threadIdx.x < 32) { nb_ = d.b[l + 1][threadIdx.x]; ng_ = d.gamma[l + 1][threadIdx.x]; nbe_ = d.beta[l + 1][threadIdx.x]; }
@@ -1517,8 +1556,8 @@ __device__ __forceinline__ void nf_cc_half_sums2(const float (&u)[OWN], const fl
         S1 = u[0];
         S2 = v[0];
         for (int m = 1; m < 32; m *= 2) {
-            S1 += __shfl_xor(S1, m, NF_WAVE);
-            S2 += __shfl_xor(S2, m, NF_WAVE);
+            S1 += nf_cc_xor(S1, m);
+            S2 += nf_cc_xor(S2, m);
         }
         which = 0;
         return;
@@ -1540,8 +1579,8 @@ __device__ __forceinline__ void nf_cc_half_sums2(const float (&u)[OWN], const fl
         const bool up = c32 & 1;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            a4[k] = (up ? u[k + 4] : u[k]) + __shfl_xor(up ? u[k] : u[k + 4], 1, NF_WAVE);
-            b4[k] = (up ? v[k + 4] : v[k]) + __shfl_xor(up ? v[k] : v[k + 4], 1, NF_WAVE);
+            a4[k] = (up ? u[k + 4] : u[k]) + nf_cc_xor(up ? u[k] : u[k + 4], 1);
+            b4[k] = (up ? v[k + 4] : v[k]) + nf_cc_xor(up ? v[k] : v[k + 4], 1);
         }
         w = up ? 4 : 0;
         m = 2;
@@ -1554,29 +1593,30 @@ __device__ __forceinline__ void nf_cc_half_sums2(const float (&u)[OWN], const fl
         const bool up = c32 & m;
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            a2[k] = (up ? a4[k + 2] : a4[k]) + __shfl_xor(up ? a4[k] : a4[k + 2], m, NF_WAVE);
-            b2[k] = (up ? b4[k + 2] : b4[k]) + __shfl_xor(up ? b4[k] : b4[k + 2], m, NF_WAVE);
+            a2[k] = (up ? a4[k + 2] : a4[k]) + nf_cc_xor(up ? a4[k] : a4[k + 2], m);
+            b2[k] = (up ? b4[k + 2] : b4[k]) + nf_cc_xor(up ? b4[k] : b4[k + 2], m);
         }
         w += up ? 2 : 0;
         m *= 2;
     }
     {
         const bool up = c32 & m;
-        S1 = (up ? a2[1] : a2[0]) + __shfl_xor(up ? a2[0] : a2[1], m, NF_WAVE);
-        S2 = (up ? b2[1] : b2[0]) + __shfl_xor(up ? b2[0] : b2[1], m, NF_WAVE);
+        S1 = (up ? a2[1] : a2[0]) + nf_cc_xor(up ? a2[0] : a2[1], m);
+        S2 = (up ? b2[1] : b2[0]) + nf_cc_xor(up ? b2[0] : b2[1], m);
         w += up ? 1 : 0;
         m *= 2;
     }
     for (; m < 32; m *= 2) {
-        S1 += __shfl_xor(S1, m, NF_WAVE);
-        S2 += __shfl_xor(S2, m, NF_WAVE);
+        S1 += nf_cc_xor(S1, m);
+        S2 += nf_cc_xor(S2, m);
     }
     which = w;
 }
 
-// grid-wide plain sums of 2 x 32 values: red[h][pb][c] -> tot[32 h + c]; fixed summation order
-template <int NPB>
-__device__ __forceinline__ const float* nf_cc_sum_exchange(float* sm, const NfCcLds& L, unsigned long long* slots, unsigned gbase, int round) {
+// grid-wide plain sums of 2 x 32 values: red[h][pb][c] -> tot[32 h + c]; fixed summation order.  peek(): as in nf_cc_stats_exchange
+template <int NPB, typename Peek>
+__device__ __forceinline__ const float* nf_cc_sum_exchange(float* sm, const NfCcLds& L, unsigned long long* slots, unsigned gbase, int round,
+                                                           Peek&& peek) {
     float* red = sm + L.RED;
     float* xs = sm + L.RS;
     float* tot = sm + L.TOT;
@@ -1598,6 +1638,7 @@ __device__ __forceinline__ const float* nf_cc_sum_exchange(float* sm, const NfCc
                                __HIP_MEMORY_SCOPE_AGENT);
     }
     if (G == 1) {
+        peek();
         __syncthreads();
         return tot;
     }
@@ -1628,6 +1669,7 @@ __device__ __forceinline__ const float* nf_cc_sum_exchange(float* sm, const NfCc
         nrows = (G + NF_CC_GROUP - 1) / NF_CC_GROUP;
     }
     nf_cc_collect_slots(xs, rs, gen, nrows, XS);
+    peek();
     __syncthreads();
     {
         float pa = 0.f, pb = 0.f;
@@ -1865,6 +1907,8 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
         }
         if (halo) nf_cc_halo_publish<OWN>(hslots, gbase, l, g, (int)tile, y0, px, kq, hs, own);   // gn of our boundary rows, to the neighbours
         float mg[OWN], mgx[OWN];
+        unsigned long long hw[2] = {0ull, 0ull};        // the neighbours' gn rows as first seen (nf_cc_halo_peek)
+        const float* tot;
         {   // batch sums of gn and gn * xhat: the gradients of beta and gamma in either mode, the mean terms of the BatchNorm backward
             // in training mode (evaluation mode normalises with constants: no mean terms)
             float p2[OWN], S1, S2;
@@ -1877,7 +1921,9 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
                 red[pb * 32 + oc] = S1;
                 red[NPB * 32 + pb * 32 + oc] = S2;
             }
-            const float* tot = nf_cc_sum_exchange<NPB>(sm, L, slots, gbase, l);
+            tot = nf_cc_sum_exchange<NPB>(sm, L, slots, gbase, l, [&] {
+                if (halo) nf_cc_halo_peek(hw, hslots, l, g, (int)tile, y0);
+            });
             NF_CC_STAMP(68 + 6 * (4 - l));
             if (blockIdx.x == 0 && threadIdx.x < 64) {
                 (threadIdx.x < 32 ? d.sum_g[l] : d.sum_gx[l])[threadIdx.x & 31] = tot[threadIdx.x];
@@ -1890,21 +1936,6 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
                 const int oc = nf_cv_cd_row(OWN * kq + rr, hs);
                 mg[rr] = training ? tot[oc] * invN : 0.f;
                 mgx[rr] = training ? tot[32 + oc] * invN : 0.f;
-            }
-            if (halo && threadIdx.x < 32 * g.W) {       // G_l at the neighbours' boundary rows: the same per-pixel formula, their gn
-                const int c = threadIdx.x >> g.lgW;
-                const float mgc = training ? tot[c] * invN : 0.f, mgxc = training ? tot[32 + c] * invN : 0.f;
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    float v = 0.f;
-                    const int f = nf_cc_halo_poll(hslots, gbase, l, g, (int)tile, y0, s2, v);
-                    if (f >= 0) {
-                        const float xhh = (a_h[s2] - kc[64 + c]) * kc[96 + c];
-                        float G = kc[c] * (v - mgc - xhh * mgxc);
-                        if ((l & 1) == 0) { G += gstream_h[s2]; gstream_h[s2] = G; }
-                        nf_cc_frame_store1(Fr, CSr, c, f, G);
-                    }
-                }
             }
         }
         // G_l = BatchNorm backward (+ the residual stream's gradient), into the other frame
@@ -1927,6 +1958,21 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
         }
         if constexpr (OWN == 2) nf_cc_frame_store2(Fr, CSr, nf_cv_cd_row(OWN * kq, hs), fpos, own[0], own[1]);
         if constexpr (OWN == 1) nf_cc_frame_store1(Fr, CSr, nf_cv_cd_row(kq, hs), fpos, own[0]);
+        if (halo && threadIdx.x < 32 * g.W) {           // G_l at the neighbours' boundary rows: the same per-pixel formula, their gn
+            const int c = threadIdx.x >> g.lgW;
+            const float mgc = training ? tot[c] * invN : 0.f, mgxc = training ? tot[32 + c] * invN : 0.f;
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                float v = 0.f;
+                const int f = nf_cc_halo_poll(hslots, gbase, l, g, (int)tile, y0, s2, v, hw[s2]);
+                if (f >= 0) {
+                    const float xhh = (a_h[s2] - kc[64 + c]) * kc[96 + c];
+                    float G = kc[c] * (v - mgc - xhh * mgxc);
+                    if ((l & 1) == 0) { G += gstream_h[s2]; gstream_h[s2] = G; }
+                    nf_cc_frame_store1(Fr, CSr, c, f, G);
+                }
+            }
+        }
         NF_CC_STAMP(69 + 6 * (4 - l));
         if (l >= 1) {                                   // transposed 3 x 3 convolution l: G_l -> layer l - 1
             if (!packed) {
