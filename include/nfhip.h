@@ -1174,6 +1174,34 @@ int nf_multi_copy(const nf_copy_desc* descs, int n_tensors, nf_stream_t stream);
 /* dst[0 .. n) = 0 (the train step's memsets: the flat gradient bucket of main.py:84's optimizer.zero_grad(), the scratch arena)          */
 int nf_zero_fill(float* dst, int64_t n, nf_stream_t stream);
 
+/* ---- planar flow (flows/planar.py), the whole stack of K PlanarTransform layers per direction -------------------------------
+ * params / grads: 3 K device pointers on the HOST: u_0 .. u_{K-1} (D), w_0 .. w_{K-1} (D), b_0 .. b_{K-1} (1), layer order.
+ * K <= NF_PLANAR_MAX_LAYERS; D >= 1 (the kernels are specialised for D <= 8, a generic form serves larger D).                      */
+#define NF_PLANAR_MAX_LAYERS 128
+#define NF_PLANAR_INV_WG_MAX_ROWS 16384   /* the one-workgroup inverse serves B up to this (16 rows per thread of 1024)              */
+/* PlanarTransform._make_invertible (planar.py:23-33) of every layer, IN PLACE on u: where w.u < -1,
+ * u <- u + (-1 + softplus(w.u) - w.u) * w / |w|^2.  A launch of its own, enqueued before nf_planar_fwd.                          */
+int nf_planar_project(const int64_t* params, int K, int D, nf_stream_t stream);
+/* PlanarTransform.forward of layers 0 .. K-1 (planar.py:35-45), one launch: a = z.w + b, z <- z + u tanh(a),
+ * ld += log(|1 + (w.u)(1 - tanh^2 a)| + 1e-5).  save (training, may be NULL): the K layer inputs, save[(k B + b) D + d].              */
+int nf_planar_fwd(const float* z, float* out, float* ld, float* save, const int64_t* params, int K, int64_t B, int D,
+                  nf_stream_t stream);
+/* floats of the `slab` nf_planar_bwd needs (written to *n_floats)                                                                  */
+int nf_planar_bwd_slab_floats(int K, int64_t B, int D, int64_t* n_floats);
+/* autograd of nf_planar_fwd from its `save`: g_z (may be NULL for D <= 8) and the parameter gradients ACCUMULATED INTO grads (+=).
+ * The batch sums go through `slab` (per-wave partial sums) and a fixed-order fold launch: no float atomics, bit-reproducible.        */
+int nf_planar_bwd(const float* g_out, const float* g_ld, const float* save, const int64_t* params, const int64_t* grads,
+                  float* g_z, float* slab, int K, int64_t B, int D, nf_stream_t stream);
+/* PlanarTransform.backward of layers K-1 .. 0 (planar.py:47-68), no projection: per layer the bisection from [-1e3, 1e3], stopped
+ * after the FIRST iteration at which every row of the batch has |hi - lo| < 1e-5 (100 at most); then a = (lo + hi)/2 + b,
+ * z <- z - u tanh(a), ld -= log(|1 + (w.u)(1 - tanh^2 a)| + 1e-5).  out may equal z.  iters (int[K], device): the iteration count
+ * of each layer.  mids (may be NULL): the midpoints (lo + hi)/2, mids[k B + b].  B <= NF_PLANAR_INV_WG_MAX_ROWS: one workgroup;
+ * else (or after nf_planar_config(1)) three launches per layer with scratch (2 B floats) and ctl (2 K ints).                       */
+int nf_planar_inv(const float* z, float* out, float* ld, float* mids, int* iters, float* scratch, int* ctl, const int64_t* params,
+                  int K, int64_t B, int D, nf_stream_t stream);
+/* form selector of nf_planar_inv: 0 = by B (default), 1 = the grid form at every B (tests run both forms at the same sizes)          */
+int nf_planar_config(int mode);
+
 #ifdef __cplusplus
 }
 #endif

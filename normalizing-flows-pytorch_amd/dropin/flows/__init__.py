@@ -24,6 +24,7 @@ Resolution rules of this package:
   ``_nf_reference_flows`` (without executing its ``__init__``) and ``flows.planar / ffjord / cnf / odeint`` forward to
   it, so their relative imports (``from .modules import Compose, BatchNorm, deriv_tanh``, planar.py:6) see the
   reference's modules, not the engine's.  Without a reference checkout they raise ``NotImplementedError`` on use.
+  ``NF_DROPIN_PLANAR=1`` makes ``PlanarFlow`` and ``flows.planar`` the engine's instead (HIP kernels, no reference needed).
 
 ``python main.py`` puts the script's directory BEFORE ``PYTHONPATH`` on ``sys.path``, so the reference's own ``flows``
 would win the plain path search; ``dropin/sitecustomize.py`` (imported by the interpreter at start-up because
@@ -95,6 +96,10 @@ def _outside(name, module):
     return _Missing
 
 
-PlanarFlow, Ffjord = _outside('PlanarFlow', 'planar'), _outside('Ffjord', 'ffjord')
+# NF_DROPIN_PLANAR=1: the engine's PlanarFlow (HIP forward / backward / bisection inverse) and ``flows.planar`` its module; 0 (default):
+# the reference's own class as above
+PLANAR_ENGINE = os.environ.get('NF_DROPIN_PLANAR', '0') == '1'
+PlanarFlow = _pkg.PlanarFlow if PLANAR_ENGINE else _outside('PlanarFlow', 'planar')
+Ffjord = _outside('Ffjord', 'ffjord')
 
 __all__ = ['PlanarFlow', 'RealNVP', 'Glow', 'Flowpp', 'MAF', 'ResFlow', 'Ffjord']

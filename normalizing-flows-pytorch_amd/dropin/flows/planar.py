@@ -1,6 +1,10 @@
-"""flows.planar is outside the accelerated path: served by the user's reference checkout (see flows/__init__.py)."""
+"""flows.planar: the reference's own module from the user's checkout by default (see flows/__init__.py); with NF_DROPIN_PLANAR=1 the
+engine's PlanarFlow / PlanarTransform (HIP kernels) under the reference's names."""
 import sys
 
-from . import reference_module
+from . import PLANAR_ENGINE, _pkg, reference_module
 
-sys.modules[__name__] = reference_module('planar')
+if PLANAR_ENGINE:
+    PlanarFlow, PlanarTransform, Compose, BatchNorm = _pkg.PlanarFlow, _pkg.PlanarTransform, _pkg.Compose, _pkg.BatchNorm
+else:
+    sys.modules[__name__] = reference_module('planar')

@@ -1007,6 +1007,134 @@ def mixlogcdf(x, log_pi, mu, s, ld, inverse=False):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# planar flow (flows/planar.py): a run of K PlanarTransform layers per launch
+# ----------------------------------------------------------------------------------------------------------------------
+PLANAR_GRID = False           # (tests: nf_planar_config(1), the grid form of the inverse at every batch size)
+
+
+def planar_config(grid):
+    """select the forms of nf_planar_inv: ``grid=True`` takes the three-launch-per-layer grid form at every batch size"""
+    global PLANAR_GRID
+    PLANAR_GRID = bool(grid)
+    N.call('nf_planar_config', 1 if PLANAR_GRID else 0)
+
+
+def _planar_check(z):
+    if z.dim() != 2:
+        raise RuntimeError('PlanarFlow takes (B, D) input (planar.py:39 multiplies z by w.t() with torch.mm), got shape %s'
+                           % (tuple(z.shape), ))
+
+
+def _planar_table(tensors):
+    """host array of device pointers u_0 .. u_{K-1}, w_0 .., b_0 .. (include/nfhip.h: the params / grads tables)"""
+    return (ctypes.c_int64 * len(tensors))(*[N.ptr(t) for t in tensors])
+
+
+def _planar_params(layers):
+    return [m.u for m in layers] + [m.w for m in layers] + [m.b for m in layers]
+
+
+def planar_project_(layers):
+    """PlanarTransform._make_invertible of every layer (planar.py:23-33): u projected IN PLACE through the parameter's current
+    storage (a view of the flat bucket after GradBucket(flatten_params=True)), one launch, no host round trip"""
+    with torch.no_grad():
+        K, D = len(layers), layers[0].u.shape[1]
+        N.call('nf_planar_project', _planar_table([p.data for p in _planar_params(layers)]), K, D, N.stream())
+
+
+class _PlanarFlow(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, ld, K, *params):
+        B, D = z.shape
+        out = torch.empty_like(z)
+        save = torch.empty(K * B * D, dtype=z.dtype, device=z.device)
+        N.call('nf_planar_fwd', N.ptr(z), N.ptr(out), N.ptr(ld), N.ptr(save), _planar_table(params), K, B, D, N.stream())
+        ctx.K = K
+        ctx.sinks = _sinks(*params)
+        ctx.save_for_backward(save, *params)
+        ctx.mark_dirty(ld)
+        return out, ld
+
+    @staticmethod
+    def backward(ctx, g_out, g_ld):
+        save, *params = ctx.saved_tensors
+        K = ctx.K
+        D = params[0].shape[1]
+        B = save.numel() // (K * D)
+        g_out, g_ld = _contig(g_out), _contig(g_ld)
+        want_z = ctx.needs_input_grad[0]
+        g_z = torch.empty((B, D), dtype=g_out.dtype, device=g_out.device) if (want_z or D > 8) else None
+        n = ctypes.c_int64(0)
+        rc = N.load().nf_planar_bwd_slab_floats(K, B, D, ctypes.byref(n))
+        if rc != 0:
+            raise N.NativeLibraryError('nf_planar_bwd_slab_floats failed with code %d' % rc)
+        slab = torch.empty(max(int(n.value), 1), dtype=torch.float32, device=g_out.device)
+        if ctx.sinks is not None:
+            grads, ret = ctx.sinks, [None] * (3 * K)
+        else:
+            flat = WS.zeros(K * (2 * D + 1), g_out.device)
+            gu = flat[:K * D].view(K, 1, D)
+            gw = flat[K * D:2 * K * D].view(K, 1, D)
+            gb = flat[2 * K * D:].view(K, 1)
+            ret = [gu[k] for k in range(K)] + [gw[k] for k in range(K)] + [gb[k] for k in range(K)]
+            grads = ret
+        N.call('nf_planar_bwd', N.ptr(g_out), N.ptr(g_ld), N.ptr(save), _planar_table(params), _planar_table(grads), N.ptr(g_z),
+               N.ptr(slab), K, B, D, N.stream())
+        return (g_z if want_z else None, g_ld, None) + tuple(ret)
+
+
+PLANAR_MAX_LAYERS = 128       # include/nfhip.h NF_PLANAR_MAX_LAYERS (checked against the header in tests/test_planar_host.py)
+
+
+def planar_flow(z, ld, layers):
+    """PlanarTransform.forward of ``layers`` in order (planar.py:35-45): the projection of every u (one launch), then all layers in
+    one launch; training (autograd on) saves the layer inputs for the one-launch backward + fold"""
+    _planar_check(z)
+    z = _contig(z)
+    ld = _owned_ld(ld)
+    for i in range(0, len(layers), PLANAR_MAX_LAYERS):
+        run = layers[i:i + PLANAR_MAX_LAYERS]
+        planar_project_(run)
+        params = _planar_params(run)
+        if torch.is_grad_enabled() and (z.requires_grad or ld.requires_grad or any(p.requires_grad for p in params)):
+            z, ld = _PlanarFlow.apply(z, ld, len(run), *params)
+        else:
+            with torch.no_grad():
+                B, D = z.shape
+                out = torch.empty_like(z)
+                N.call('nf_planar_fwd', N.ptr(z), N.ptr(out), N.ptr(ld), None, _planar_table(params), len(run), B, D, N.stream())
+                z = out
+    return z, ld
+
+
+def planar_inverse(z, ld, layers, mids=False):
+    """PlanarTransform.backward of ``layers`` in reverse order (planar.py:47-68), no graph.  Returns (z, ld, iters) -- iters: int32
+    (K,), the bisection's iteration count per layer in layer order -- and, with ``mids=True``, the midpoints (K, B) as a fourth value."""
+    _planar_check(z)
+    with torch.no_grad():
+        z = _contig(z)
+        ld = _owned_ld(ld)
+        B, D = z.shape
+        K = len(layers)
+        iters = torch.zeros(K, dtype=torch.int32, device=z.device)
+        mid = torch.empty((K, B), dtype=z.dtype, device=z.device) if mids else None
+        wg = not PLANAR_GRID and B <= N.header_constant('NF_PLANAR_INV_WG_MAX_ROWS')
+        scratch = None if wg else torch.empty(2 * max(B, 1), dtype=torch.float32, device=z.device)
+        ctl = None if wg else torch.empty(2 * PLANAR_MAX_LAYERS, dtype=torch.int32, device=z.device)
+        out = torch.empty_like(z)
+        cur = z
+        for j in range(((K + PLANAR_MAX_LAYERS - 1) // PLANAR_MAX_LAYERS) - 1, -1, -1):
+            a, b = j * PLANAR_MAX_LAYERS, min(K, (j + 1) * PLANAR_MAX_LAYERS)
+            run = layers[a:b]
+            N.call('nf_planar_inv', N.ptr(cur), N.ptr(out), N.ptr(ld), N.ptr(mid[a:b]) if mids else None, N.ptr(iters[a:b]),
+                   N.ptr(scratch), N.ptr(ctl), _planar_table([p.data for p in _planar_params(run)]), len(run), B, D, N.stream())
+            cur = out
+        if mids:
+            return cur, ld, iters, mid
+        return cur, ld, iters
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # NLL under the standard-normal prior (training harness, main.py:49-51, :85)
 # ----------------------------------------------------------------------------------------------------------------------
 class _NLL(torch.autograd.Function):

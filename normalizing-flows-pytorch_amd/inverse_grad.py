@@ -14,7 +14,9 @@ What the reference's OWN graph contains is reproduced, no more:
   * flow ``BatchNorm`` statistics are buffers (flows/modules.py:309-316): constants of the graph;
   * ``MixLogCDF.backward`` returns the bisection's midpoint, a constant of the graph (flows/modules.py:196-208: ``lo`` / ``hi`` are built
     from ``torch.where`` over constants); the coupling's parameters receive gradient through the affine part, the sigmoid's log-det and
-    ``- log pdf(x)`` (flows/coupling.py:192-210, flows/modules.py:209-212).
+    ``- log pdf(x)`` (flows/coupling.py:192-210, flows/modules.py:209-212);
+  * ``PlanarTransform.backward`` bisects the same way (flows/planar.py:53-61): its midpoint is a constant, ``b``, ``u`` and ``w`` receive
+    gradient through ``affine = mid + b``, ``z - u tanh(affine)`` and the log-det term (planar.py:63-66).
 Not served (NotImplementedError, as before): the MAF inverse (the reference writes columns of ``z`` in place between conditioner calls,
 flows/maf.py:109-119: its own graph does not survive that) and the fixed-point inverse of the residual blocks.
 """
@@ -142,5 +144,13 @@ def layer_inverse(layer, y, ld):
         uu = (x.unsqueeze(1) - mu) * torch.exp(-s)                   # mix_logistic_logpdf, modules.py:64-78
         logpdf = torch.logsumexp(logpi + uu - s - 2.0 * F.softplus(uu), dim=1)
         return _merge(x, z1, y, layer.mode, layer.odd), ld - _per_sample(logpdf)
+    if isinstance(layer, L.PlanarTransform):                         # planar.py:47-68 (no projection in the inverse)
+        with torch.no_grad():                                        # the bisection's midpoint: a constant of the reference's graph too
+            _, _, _, mid = NF.planar_inverse(y.detach(), torch.zeros(y.shape[0], dtype=y.dtype, device=y.device), [layer], mids=True)
+        affine = mid[0].unsqueeze(1) + layer.b
+        w_dot_u = torch.mm(layer.u, layer.w.t())
+        th = torch.tanh(affine)
+        det = 1.0 + w_dot_u * (1.0 - th * th)
+        return y - layer.u * th, ld - torch.sum(torch.log(torch.abs(det) + 1.0e-5), dim=1)
     raise NotImplementedError('the inverse of %s has no autograd graph in this engine (see inverse_grad.py: the MAF and residual-block '
                               'inverses); detach the input or differentiate the forward direction' % type(layer).__name__)

@@ -148,9 +148,24 @@ class Compose(nn.Module):
             return False
         return FUSED.flowpp_post_actnorm_usable(z, k, a)
 
+    def _planar_run(self, i, z, step):
+        """the maximal run of PlanarTransforms without hooks from layer i on (step +1: forward order, -1: backward), on the GPU"""
+        L, run, j = self.layers, [], i
+        if not z.is_cuda:
+            return run
+        while 0 <= j < len(L) and type(L[j]) is PlanarTransform and not (L[j]._forward_hooks or L[j]._forward_pre_hooks):
+            run.append(L[j])
+            j += step
+        return run
+
     def forward(self, z, log_df_dz):
         L, n, i = self.layers, len(self.layers), 0
         while i < n:
+            run = self._planar_run(i, z, 1) if self._fuse_now else []
+            if run:                                                # the run of planar layers: projection + one launch
+                z, log_df_dz = NF.planar_flow(z, log_df_dz, run)
+                i += len(run)
+                continue
             run = self._realnvp_eval_run_at(i, z) if not torch.is_grad_enabled() else None
             if run is not None:                                    # density evaluation: the run in one launch, no exchange
                 z, log_df_dz = FUSED.realnvp_flow_vec_eval(z, log_df_dz, run)
@@ -304,6 +319,11 @@ class Compose(nn.Module):
                 return self.backward(z, log_df_dz)
         i = len(self.layers) - 1
         while i >= 0:
+            run = self._planar_run(i, z, -1) if self._fuse_now else []
+            if run:                                                # the run of planar layers: one bisection launch (or 3 per layer)
+                z, log_df_dz, _ = NF.planar_inverse(z, log_df_dz, run[::-1])
+                i -= len(run)
+                continue
             run = self._glow_inverse_run_ending_at(i, z)
             if run is not None:
                 z, log_df_dz = FUSED.glow_flow_vec_inverse(z, log_df_dz, run)
@@ -407,6 +427,44 @@ class MixLogCDF(nn.Module):
 
     def backward(self, x, log_pi, mu, s, log_df_dz):
         return NF.mixlogcdf(x, log_pi, mu, s, log_df_dz, inverse=True)
+
+
+class PlanarTransform(nn.Module):
+    """flows/planar.py:9-68.  Same parameters (u, w of shape (1, dim), b of shape (1,)), same construction draws and projection; the
+    forward projects u in place on the GPU (no ``.item()`` host sync) and a Compose runs a whole stack of these in one launch per
+    direction (functional.planar_flow / planar_inverse)."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.dim = dim
+        u = torch.randn(1, self.dim) * 0.01
+        w = torch.randn(1, self.dim) * 0.01
+        b = torch.randn(1) * 0.01
+        self.register_parameter('u', nn.Parameter(u))
+        self.register_parameter('w', nn.Parameter(w))
+        self.register_parameter('b', nn.Parameter(b))
+        self._make_invertible()
+
+    def _make_invertible(self):
+        """planar.py:23-33 with torch ops where the parameters live (construction: the CPU, as the reference); the flow itself
+        projects in its forward launch sequence (functional.planar_project_)"""
+        if self.u.is_cuda:
+            NF.planar_project_([self])
+            return
+        with torch.no_grad():
+            w_dot_u = torch.mm(self.u, self.w.t())
+            if w_dot_u.item() >= -1.0:
+                return
+            norm_w = self.w / torch.norm(self.w, p=2, dim=1)**2
+            bias = -1.0 + F.softplus(w_dot_u)
+            self.u.data = self.u + (bias - w_dot_u) * norm_w
+
+    def forward(self, z, log_df_dz):
+        return NF.planar_flow(z, log_df_dz, [self])
+
+    def backward(self, z, log_df_dz):
+        z, log_df_dz, _ = NF.planar_inverse(z, log_df_dz, [self])
+        return z, log_df_dz
 
 
 def _param_shape(num_features):

@@ -8,11 +8,12 @@ Layer stacks with the reference's constructor and call surface:
 Reference: flows/realnvp.py:9-63, flows/glow.py:10-68, flows/flowpp.py:9-78, flows/maf.py:122-148.
 The multi-scale image recipe (shared by RealNVP / Glow / Flow++) is written once here.
 """
+import numpy as np
 import torch
 import torch.nn as nn
 
 from .layers import (ActNorm, AffineCoupling, AutoregressiveTransfrom, BatchNorm, Compose, InvertibleConv1x1, Logit,
-                     MixLogAttnCoupling, Squeeze2d, Unsqueeze2d)
+                     MixLogAttnCoupling, PlanarTransform, Squeeze2d, Unsqueeze2d)
 
 
 class _FlowModel(nn.Module):
@@ -187,3 +188,32 @@ class MAF(_FlowModel):
             layers.append(BatchNorm(dims, affine=False))
             layers.append(AutoregressiveTransfrom(dims[0]))
         return layers
+
+
+class PlanarFlow(nn.Module):
+    """flows/planar.py:71-94: ``cfg.layers`` PlanarTransforms on the flattened dimension.  The reference also builds a BatchNorm per
+    layer and discards it (planar.py:82); that draws no random numbers, so it is left out here.  Only (B, D) input runs: the reference
+    constructs an image PlanarFlow but its torch.mm fails on a 4-D batch, this one raises RuntimeError naming the shape."""
+
+    def __init__(self, dims, datatype=None, cfg=None):
+        super().__init__()
+        self.dims = dims
+        self.dim = np.prod(dims)
+        self.n_layers = cfg.layers
+        self.net = Compose([PlanarTransform(self.dim) for _ in range(self.n_layers)])
+
+    _zero_ld = _FlowModel._zero_ld
+
+    def _run(self, fn, z):
+        if z.dim() != 2:
+            raise RuntimeError('PlanarFlow takes (B, D) input, got shape %s' % (tuple(z.shape), ))
+        if z.is_cuda and z.device.index != torch.cuda.current_device():
+            with torch.cuda.device(z.device):
+                return fn(z, self._zero_ld(z))
+        return fn(z, self._zero_ld(z))
+
+    def forward(self, z):
+        return self._run(self.net, z)
+
+    def backward(self, z):
+        return self._run(self.net.backward, z)
