@@ -1202,6 +1202,60 @@ int nf_planar_inv(const float* z, float* out, float* ld, float* mids, int* iters
 /* form selector of nf_planar_inv: 0 = by B (default), 1 = the grid form at every B (tests run both forms at the same sizes)          */
 int nf_planar_config(int mode);
 
+/* ---- FFJORD (flows/cnf.py, flows/odeint.py): one continuous normalizing flow layer, a whole ODE integration per launch, fp64 ----------
+ * The field is ODENet(dims=(D,)) as CNF.__init__ builds it (cnf.py:72-90, :140): three ConcatLinear layers D+1 -> 32 -> 32 -> D with
+ * softplus between them (cnf.py:114-117), column 0 of every weight multiplying t (cnf.py:48-51).  D <= NF_CNF_MAX_DIM; hidden width
+ * NF_CNF_HIDDEN and two hidden layers only (nothing else is constructible through CNF).
+ * params: 6 device pointers on the HOST, fp64: W1 (32, D+1), b1 (32), W2 (32, 33), b2 (32), W3 (D, 33), b3 (D).
+ * sched (device, fp64): [0] the final lerp slope, [1 .. 1+n_steps) the per-step dt, then n_steps * stages stage times (nf_cnf_schedule).
+ * trace: NF_CNF_TRACE_HUTCHINSON  mean over n_samples of w^T (df/dz) w (cnf.py:22-37); NF_CNF_TRACE_EXACT  sum_i df_i/dz_i (cnf.py:10-19),
+ *   both by forward-mode tangents in the same pass as the value.  Noise w: `noise` (device, float32, [E][B][n_samples][D], E = n_steps *
+ *   stages, evaluation order) or, where noise is NULL, drawn in the kernel (Philox4x32-10 + Box-Muller, float32, keyed by seed[0], the
+ *   stream offset seed[1], evaluation, row and sample; seed is DEVICE memory, int64[2]).
+ * Data tensors are float32 (is_f64 = 0) or float64 (is_f64 = 1): the casts of CNF.forward (cnf.py:146-158) happen in the kernel.      */
+#define NF_CNF_MAX_DIM 8
+#define NF_CNF_HIDDEN 32
+#define NF_CNF_MAX_SAMPLES 8
+#define NF_CNF_MAX_STEPS 4096
+#define NF_CNF_MIDPOINT 0
+#define NF_CNF_RK4 1
+#define NF_CNF_BOSHA3 2
+#define NF_CNF_DOPRI5 3
+#define NF_CNF_TRACE_HUTCHINSON 0
+#define NF_CNF_TRACE_EXACT 1
+/* HOST ONLY.  The evaluation schedule of odeint(func, x, times, method) (odeint.py:13-36 fixed step, :68-111 "adaptive": the step-size
+ * proposal is discarded, :80, so these are fixed-step methods with dt = (t_end - t_start) / (len(times) - 1), the `while` of :79, the
+ * overshoot rule of :82-83 and the final lerp of :91-92), with the same IEEE double operations in the same order.  times: n_times
+ * doubles (host).  Writes *n_steps, step_dt[n_steps] (the dt each step's stages use), stage_t[n_steps * stages] (the t handed to
+ * ODENet.forward, evaluation order), *slope (1 for the fixed-step methods).  stage_t / step_dt may be NULL to query *n_steps alone;
+ * cap_steps: the room in step_dt (and stage_t / stages); more steps than that, or than NF_CNF_MAX_STEPS, is an argument error.        */
+int nf_cnf_schedule(const double* times, int n_times, int method, double* stage_t, double* step_dt, double* slope, int* n_steps,
+                    int cap_steps);
+/* odeint(func, (z, log_df_dz), times, method) (odeint.py:201-214; CNF.forward / CNF.backward, cnf.py:145-173) in ONE launch, a row per
+ * lane: z (B, D) and ld (B) in, z_out and ld_out out (may alias the inputs).  state (fp64, (B, D+1), may be NULL): the final state
+ * before the cast, which OdeIntAdjoint.forward saves (odeint.py:261-262).                                                              */
+int nf_cnf_integrate(const void* z, const void* ld, void* z_out, void* ld_out, double* state, const int64_t* params, const double* sched,
+                     int n_steps, int method, int trace, int n_samples, const float* noise, const int64_t* seed, int is_f64, int64_t B,
+                     int D, nf_stream_t stream);
+/* doubles of the `slab` nf_cnf_adjoint needs: one slab of the 6 parameter gradients (the zero_params of odeint.py:275) per workgroup
+ * of 64 rows                                                                                                                         */
+int nf_cnf_slab_doubles(int64_t B, int D, int64_t* n_doubles);
+/* OdeIntAdjoint.backward (odeint.py:266-284) in one launch + one fold: integrates (a_z, z, log_df_dz) from `state` over `sched` (the
+ * schedule of the REVERSED times of the forward pass) with the augmented dynamics of aug_func_wrapper (odeint.py:227-247): the VJP
+ * through value and tangent passes is hand-derived (second order through softplus).  Every evaluation takes its own noise (`noise` /
+ * `seed` as above, E evaluations of this pass).  g_zo (B, D), g_ldo (B): the incoming gradients; g_z, g_ld: written.  Parameter
+ * gradients are accumulated in fp64 per workgroup over the whole integration, written to `slab` and summed in a fixed order by the fold
+ * launch into grads (fp64, flat in params order, OVERWRITTEN): no float atomics, bit-reproducible.                                   */
+int nf_cnf_adjoint(const double* state, const void* g_zo, const void* g_ldo, void* g_z, void* g_ld, double* slab, double* grads,
+                   const int64_t* params, const double* sched, int n_steps, int method, int trace, int n_samples, const float* noise,
+                   const int64_t* seed, int is_f64, int64_t B, int D, nf_stream_t stream);
+/* the in-kernel noise of a pass written out: out (float32, [E][B][n_samples][D]) holds exactly what nf_cnf_integrate / nf_cnf_adjoint
+ * draw for the same seed words (a test feeds it back as explicit noise; cnf.py:29 is the reference's draw)                           */
+int nf_cnf_noise(float* out, const int64_t* seed, int64_t E, int64_t B, int n_samples, int D, nf_stream_t stream);
+/* the fold alone: grads[e] = sum over the n_slabs slabs of slab[s * P + e], fixed order (P: parameter count of the field at D): the
+ * adj_params OdeIntAdjoint.backward returns (odeint.py:282-284)                                                                       */
+int nf_cnf_fold(const double* slab, int64_t n_slabs, double* grads, int D, nf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,8 +103,9 @@ def stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def ptr(t):
-    """device pointer of a contiguous fp32/int32 GPU tensor (None -> NULL)."""
+def ptr(t, dtypes=(torch.float32, torch.int32)):
+    """device pointer of a contiguous fp32/int32 GPU tensor (None -> NULL); ``dtypes`` names what else an entry point takes (the fp64
+    tensors of the CNF kernels)."""
     if t is None:
         return None
     if not t.is_cuda:
@@ -112,8 +113,9 @@ def ptr(t):
                                  'path' % t.device)
     if not t.is_contiguous():
         raise NativeLibraryError('nfhip kernels need contiguous tensors')
-    if t.dtype not in (torch.float32, torch.int32):
-        raise NativeLibraryError('nfhip kernels are fp32 (int32 for flags), got %s' % t.dtype)
+    if t.dtype not in dtypes:
+        raise NativeLibraryError('nfhip kernels are fp32 (int32 for flags), got %s' % t.dtype if torch.float32 in dtypes else
+                                 'this nfhip entry point takes %s, got %s' % (' / '.join(str(d) for d in dtypes), t.dtype))
     if t.device.index != torch.cuda.current_device():
         # launches go to the CURRENT device's stream and read that device's copy of the library's globals (spin limit, error word,
         # deterministic mode): a tensor of another GPU would be dereferenced from the wrong device

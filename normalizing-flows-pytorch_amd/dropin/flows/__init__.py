@@ -24,7 +24,8 @@ Resolution rules of this package:
   ``_nf_reference_flows`` (without executing its ``__init__``) and ``flows.planar / ffjord / cnf / odeint`` forward to
   it, so their relative imports (``from .modules import Compose, BatchNorm, deriv_tanh``, planar.py:6) see the
   reference's modules, not the engine's.  Without a reference checkout they raise ``NotImplementedError`` on use.
-  ``NF_DROPIN_PLANAR=1`` makes ``PlanarFlow`` and ``flows.planar`` the engine's instead (HIP kernels, no reference needed).
+  ``NF_DROPIN_PLANAR=1`` makes ``PlanarFlow`` and ``flows.planar`` the engine's instead (HIP kernels, no reference needed);
+  ``NF_DROPIN_FFJORD=1`` does the same for ``Ffjord`` and ``flows.ffjord / cnf / odeint``.
 
 ``python main.py`` puts the script's directory BEFORE ``PYTHONPATH`` on ``sys.path``, so the reference's own ``flows``
 would win the plain path search; ``dropin/sitecustomize.py`` (imported by the interpreter at start-up because
@@ -100,6 +101,9 @@ def _outside(name, module):
 # the reference's own class as above
 PLANAR_ENGINE = os.environ.get('NF_DROPIN_PLANAR', '0') == '1'
 PlanarFlow = _pkg.PlanarFlow if PLANAR_ENGINE else _outside('PlanarFlow', 'planar')
-Ffjord = _outside('Ffjord', 'ffjord')
+# NF_DROPIN_FFJORD=1: the engine's Ffjord (one launch per CNF layer and direction, adjoint gradient) and ``flows.ffjord / cnf / odeint``
+# its modules; 0 (default): the reference's own classes
+FFJORD_ENGINE = os.environ.get('NF_DROPIN_FFJORD', '0') == '1'
+Ffjord = _pkg.Ffjord if FFJORD_ENGINE else _outside('Ffjord', 'ffjord')
 
 __all__ = ['PlanarFlow', 'RealNVP', 'Glow', 'Flowpp', 'MAF', 'ResFlow', 'Ffjord']

@@ -1135,6 +1135,176 @@ def planar_inverse(z, ld, layers, mids=False):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# FFJORD (flows/cnf.py, flows/odeint.py): a whole ODE integration of one CNF layer per launch, fp64 (csrc/cnf.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+CNF_METHODS = {'midpoint': 0, 'rk4': 1, 'bosha3': 2, 'dopri5': 3}      # include/nfhip.h NF_CNF_MIDPOINT ..; odeint.py:163-168
+CNF_STAGES = (2, 4, 5, 7)                                               # field evaluations per step
+CNF_TRACES = {'hutchinson': 0, 'exact': 1}
+_F64 = (torch.float64, )
+_F3264 = (torch.float32, torch.float64)
+
+
+def _cnf_method(method):
+    try:
+        return CNF_METHODS[method]
+    except KeyError:
+        raise KeyError(method)                                              # (SOLVERS[method], odeint.py:211)
+
+
+def cnf_schedule(times, method):
+    """the evaluation schedule of ``odeint(func, x, times, method)`` (odeint.py:13-20, :68-94) as float64 CPU tensors:
+    (stage_t [steps * stages], step_dt [steps], slope).  Host only: no GPU is touched."""
+    m = _cnf_method(method)
+    tt = torch.as_tensor(times).detach().to('cpu', torch.float64).contiguous()
+    lib = N.load()
+    n, slope = ctypes.c_int(0), ctypes.c_double(0.0)
+    rc = lib.nf_cnf_schedule(tt.data_ptr(), tt.numel(), m, None, None, ctypes.byref(slope), ctypes.byref(n), 0)
+    if rc != 0:
+        raise N.NativeLibraryError('nf_cnf_schedule failed with code %d' % rc)
+    steps = int(n.value)
+    stage_t = torch.empty(steps * CNF_STAGES[m], dtype=torch.float64)
+    step_dt = torch.empty(steps, dtype=torch.float64)
+    rc = lib.nf_cnf_schedule(tt.data_ptr(), tt.numel(), m, stage_t.data_ptr(), step_dt.data_ptr(), ctypes.byref(slope),
+                             ctypes.byref(n), steps)
+    if rc != 0:
+        raise N.NativeLibraryError('nf_cnf_schedule failed with code %d' % rc)
+    return stage_t, step_dt, float(slope.value)
+
+
+def cnf_pack_schedule(times, method, device):
+    """(packed device schedule [slope, dt .., stage_t ..], steps) as nf_cnf_integrate takes it"""
+    stage_t, step_dt, slope = cnf_schedule(times, method)
+    packed = torch.cat([torch.tensor([slope], dtype=torch.float64), step_dt, stage_t])
+    return packed.to(device), step_dt.numel()
+
+
+def _cnf_check(z, params):
+    if not z.is_cuda:
+        N.ptr(z)                                                            # raises the engine's "no CPU path" error
+    if z.dim() != 2:
+        raise RuntimeError('CNF takes (B, D) input, got shape %s' % (tuple(z.shape), ))
+    D = z.shape[1]
+    H = N.header_constant('NF_CNF_HIDDEN')
+    if D > N.header_constant('NF_CNF_MAX_DIM'):
+        raise RuntimeError('the CNF kernels serve D <= %d features, got %d' % (N.header_constant('NF_CNF_MAX_DIM'), D))
+    want = [(H, D + 1), (H, ), (H, H + 1), (H, ), (D, H + 1), (D, )]
+    if len(params) != 6 or [tuple(p.shape) for p in params] != want:
+        raise RuntimeError('the CNF kernels serve the field CNF.__init__ builds (D+1 -> 32 -> 32 -> D), got parameter shapes %s'
+                           % ([tuple(p.shape) for p in params], ))
+    if z.dtype not in _F3264:
+        raise RuntimeError('CNF takes float32 or float64 data, got %s' % z.dtype)
+
+
+def _cnf_table(params):
+    return (ctypes.c_int64 * 6)(*[N.ptr(p, _F64) for p in params])
+
+
+def _cnf_noise_ok(noise, E, B, S, D, trace):
+    if noise is None or trace == CNF_TRACES['exact']:
+        return None
+    if tuple(noise.shape) != (E, B, S, D) or noise.dtype != torch.float32:
+        raise RuntimeError('CNF noise must be float32 of shape (E, B, S, D) = %s, got %s %s'
+                           % ((E, B, S, D), noise.dtype, tuple(noise.shape)))
+    return _contig(noise)
+
+
+def cnf_integrate(z, ld, params, sched, steps, method, trace='hutchinson', n_samples=1, noise=None, seed=None, want_state=False):
+    """``odeint(func, (z, ld), times, method)`` of the field with the six float64 ``params`` in ONE launch, no graph.  ``sched, steps``:
+    cnf_pack_schedule(times, method, device).  noise: float32 (E, B, n_samples, D) in evaluation order, or None with ``seed`` (device
+    int64[2]: seed, stream offset) for in-kernel draws.  Returns (z, ld) in the input's dtype -- and, with ``want_state``, the final
+    float64 state (B, D + 1) OdeIntAdjoint saves (odeint.py:261-262)."""
+    with torch.no_grad():
+        params = [p.detach() for p in params]
+        _cnf_check(z, params)
+        m, tr = _cnf_method(method), CNF_TRACES[trace]
+        B, D = z.shape
+        z = _contig(z)
+        ld = _contig(ld.to(z.dtype))
+        noise = _cnf_noise_ok(noise, steps * CNF_STAGES[m], B, n_samples, D, tr)
+        out, ld_out = torch.empty_like(z), torch.empty_like(ld)
+        state = torch.empty((B, D + 1), dtype=torch.float64, device=z.device) if want_state else None
+        N.call('nf_cnf_integrate', N.ptr(z, _F3264), N.ptr(ld, _F3264), N.ptr(out, _F3264), N.ptr(ld_out, _F3264), N.ptr(state, _F64),
+               _cnf_table(params), N.ptr(sched, _F64), steps, m, tr, n_samples, N.ptr(noise),
+               N.ptr(seed, (torch.int64, )) if noise is None and tr == 0 else None, 1 if z.dtype == torch.float64 else 0, B, D,
+               N.stream())
+    if want_state:
+        return out, ld_out, state
+    return out, ld_out
+
+
+def cnf_noise(seed, E, B, S, D):
+    """the (E, B, S, D) float32 noise the CNF kernels draw for the seed words ``seed`` (device int64[2]) as they stand now"""
+    out = torch.empty((E, B, S, D), dtype=torch.float32, device=seed.device)
+    N.call('nf_cnf_noise', N.ptr(out), N.ptr(seed, (torch.int64, )), E, B, S, D, N.stream())
+    return out
+
+
+def cnf_param_count(D):
+    H = N.header_constant('NF_CNF_HIDDEN')
+    return H * (D + 1) + H + H * (H + 1) + H + D * (H + 1) + D
+
+
+class _CNFIntegrate(torch.autograd.Function):
+    """OdeIntAdjoint (odeint.py:250-284) for both directions of a CNF: the forward saves the final float64 state only, the backward
+    integrates (a_z, z, ld) over the reversed schedule in one launch and folds the parameter gradients in a second.  ``cfg``:
+    (sched, steps, sched_rev, steps_rev, method, trace, n_samples, draw) -- draw(E) gives the backward pass's noise at backward time
+    (fresh draws, as the reference's: odeint.py:237 evaluates the field again), or None for in-kernel noise from ``seed``."""
+
+    @staticmethod
+    def forward(ctx, z, ld, cfg, noise, noise_bwd, seed, *params):
+        sched, steps, sched_rev, steps_rev, method, trace, S, draw = cfg
+        out, ld_out, state = cnf_integrate(z, ld, params, sched, steps, method, trace, S, noise, seed, want_state=True)
+        ctx.cfg, ctx.noise_bwd, ctx.seed = cfg, noise_bwd, seed
+        ctx.f64 = z.dtype == torch.float64
+        ctx.save_for_backward(state, *params)
+        return out, ld_out
+
+    @staticmethod
+    def backward(ctx, g_z, g_ld):
+        state, *params = ctx.saved_tensors
+        _, _, sched, steps, method, trace, S, draw = ctx.cfg
+        m, tr = _cnf_method(method), CNF_TRACES[trace]
+        B, D = state.shape[0], state.shape[1] - 1
+        dt = torch.float64 if ctx.f64 else torch.float32
+        g_z, g_ld = _contig(g_z.to(dt)), _contig(g_ld.to(dt))
+        E = steps * CNF_STAGES[m]
+        noise = ctx.noise_bwd
+        if noise is None and tr == 0 and draw is not None:
+            noise = draw(E)
+        noise = _cnf_noise_ok(noise, E, B, S, D, tr)
+        seed = ctx.seed if noise is None and tr == 0 else None
+        if seed is not None:
+            seed[1] += 1                                                    # a stream of its own for this pass (device side, no sync)
+        n = ctypes.c_int64(0)
+        rc = N.load().nf_cnf_slab_doubles(B, D, ctypes.byref(n))
+        if rc != 0:
+            raise N.NativeLibraryError('nf_cnf_slab_doubles failed with code %d' % rc)
+        slab = torch.empty(max(int(n.value), 1), dtype=torch.float64, device=state.device)
+        flat = torch.empty(cnf_param_count(D), dtype=torch.float64, device=state.device)
+        a_z, a_ld = torch.empty_like(g_z), torch.empty_like(g_ld)
+        with torch.no_grad():
+            N.call('nf_cnf_adjoint', N.ptr(state, _F64), N.ptr(g_z, _F3264), N.ptr(g_ld, _F3264), N.ptr(a_z, _F3264), N.ptr(a_ld, _F3264),
+                   N.ptr(slab, _F64), N.ptr(flat, _F64), _cnf_table([p.detach() for p in params]), N.ptr(sched, _F64), steps, m, tr, S,
+                   N.ptr(noise), N.ptr(seed, (torch.int64, )), 1 if ctx.f64 else 0, B, D, N.stream())
+        grads, o = [], 0
+        for p in params:
+            grads.append(flat[o:o + p.numel()].view(p.shape))
+            o += p.numel()
+        return (a_z, a_ld, None, None, None, None) + tuple(grads)
+
+
+def cnf_flow(z, ld, params, cfg, noise=None, noise_bwd=None, seed=None):
+    """one direction of a CNF layer (cnf.py:145-173 with backprop='adjoint'): the autograd Function where a gradient is wanted, the
+    plain launch otherwise"""
+    _cnf_check(z, params)
+    ld = ld.to(z.dtype)
+    sched, steps, _, _, method, trace, S, _ = cfg
+    if torch.is_grad_enabled() and (z.requires_grad or ld.requires_grad or any(p.requires_grad for p in params)):
+        return _CNFIntegrate.apply(z, ld, cfg, noise, noise_bwd, seed, *params)
+    return cnf_integrate(z, ld, params, sched, steps, method, trace, S, noise, seed)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # NLL under the standard-normal prior (training harness, main.py:49-51, :85)
 # ----------------------------------------------------------------------------------------------------------------------
 class _NLL(torch.autograd.Function):

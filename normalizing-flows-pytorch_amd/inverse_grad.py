@@ -152,5 +152,7 @@ def layer_inverse(layer, y, ld):
         th = torch.tanh(affine)
         det = 1.0 + w_dot_u * (1.0 - th * th)
         return y - layer.u * th, ld - torch.sum(torch.log(torch.abs(det) + 1.0e-5), dim=1)
+    if isinstance(layer, L.CNF):                                     # cnf.py:160-173: the same adjoint Function, times as stored
+        return layer.backward(y, ld)
     raise NotImplementedError('the inverse of %s has no autograd graph in this engine (see inverse_grad.py: the MAF and residual-block '
                               'inverses); detach the input or differentiate the forward direction' % type(layer).__name__)

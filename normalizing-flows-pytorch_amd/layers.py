@@ -467,6 +467,166 @@ class PlanarTransform(nn.Module):
         return z, log_df_dz
 
 
+class ConcatLinear(nn.Module):
+    """flows/cnf.py:40-51: a Linear on [t, x]; column 0 of the weight multiplies t.  A parameter holder here: the field runs inside the
+    CNF kernels (functional.cnf_flow), never layer by layer."""
+
+    def __init__(self, in_features, out_features):
+        super().__init__()
+        self.linear = nn.Linear(in_features + 1, out_features)
+
+    def forward(self, t, x):
+        raise NotImplementedError('the engine evaluates the field inside the CNF integration kernels (csrc/cnf.hip); call CNF / '
+                                  'flows.odeint.odeint on the ODENet instead of its layers')
+
+
+class ODENet(nn.Module):
+    """flows/cnf.py:68-121 for density data: three ConcatLinear layers dims[0]+1 -> 32 -> 32 -> dims[0] with softplus between them, same
+    construction draws and parameter names.  ``noise_on_cpu`` (default False: the Hutchinson noise is drawn in the kernel, Philox keyed
+    by torch.initial_seed() and a per-pass stream offset): True draws it per evaluation from the CPU default generator in float32,
+    in the reference's order (cnf.py:29), the backward pass's draws included, and ships a pass's draws in one copy.
+    ``noise_source`` (tests): a callable (E, B, S, D) -> float32 tensor that replaces the draws of every pass."""
+
+    def __init__(self, dims, base_filters=32, n_layers=2, trace_estimator='hutchinson', noise_on_cpu=False):
+        super().__init__()
+        self.estimator = trace_estimator
+        self.noise_on_cpu = bool(noise_on_cpu)
+        self.noise_source = None
+        self._seed = None
+        if len(dims) == 3:
+            raise NotImplementedError('Sorry, FFJORD for image generation is not supported!')
+        if len(dims) != 1:
+            raise Exception('unsupported target dimension: %s' % (str(dims)))
+        hidden_dims = [dims[0]] + [base_filters] * n_layers + [dims[0]]
+        self.layers = nn.ModuleList([ConcatLinear(i, o) for i, o in zip(hidden_dims[:-1], hidden_dims[1:])])
+
+    def trace_mode(self):
+        """(trace, samples) as ODENet._get_trace_estimator picks them (cnf.py:92-105): training forces Hutchinson with one sample"""
+        if self.training:
+            return 'hutchinson', 1
+        if self.estimator == 'exact':
+            return 'exact', 1
+        if self.estimator == 'hutchinson':
+            return 'hutchinson', 4
+        raise RuntimeError('unknown trace estimator %r' % (self.estimator, ))
+
+    def field_params(self):
+        return [p for m in self.layers for p in (m.linear.weight, m.linear.bias)]
+
+    def draw(self, E, B, S, D, device):
+        """the noise of one pass, (E, B, S, D) float32 on ``device``, or None for in-kernel draws"""
+        if self.noise_source is not None:
+            return self.noise_source(E, B, S, D).to(device=device, dtype=torch.float32)
+        if not self.noise_on_cpu:
+            return None
+        w = torch.stack([torch.randn([B, S, D]) for _ in range(E)])        # cnf.py:29, one draw per field evaluation
+        return w.to(device, non_blocking=True)
+
+    def seed(self, device):
+        """device int64[2] (seed, stream offset) of the in-kernel noise; the offset moves on with every pass"""
+        if self._seed is None or self._seed.device != device:
+            self._seed = torch.tensor([torch.initial_seed() & 0x7fffffffffffffff, 0], dtype=torch.int64, device=device)
+        self._seed[1] += 1
+        return self._seed
+
+    def forward(self, t, states):
+        raise NotImplementedError('the engine evaluates the field inside the CNF integration kernels (csrc/cnf.hip); use CNF or '
+                                  'flows.odeint.odeint(func, states, times, method)')
+
+
+def odeint(func, x, times, method, noise=None, noise_bwd=None):
+    """flows/odeint.py:201-214 and :217-224 on the engine's ODENet: the whole integration in one launch; with autograd on and a gradient
+    wanted it is the adjoint form (the only one the engine has).  x: (z, log_df_dz); returns the pair at times[-1]."""
+    if not isinstance(func, ODENet):
+        raise TypeError('the engine integrates its own ODENet only, got %s' % type(func).__name__)
+    if isinstance(x, torch.Tensor) or not isinstance(x, tuple) or len(x) != 2:
+        raise Exception('"odeint" input must be the tuple (z, log_df_dz)')
+    z, ld = x
+    params = func.field_params()
+    if not z.is_cuda:
+        N.ptr(z)
+    trace, S = func.trace_mode()
+    dev = z.device
+    times = torch.as_tensor(times).detach()
+    sched, steps = NF.cnf_pack_schedule(times, method, dev)
+    sched_rev, steps_rev = NF.cnf_pack_schedule(torch.flip(times, dims=[0]), method, dev)
+    B, D = z.shape
+    cfg = (sched, steps, sched_rev, steps_rev, method, trace, S,
+           lambda E: func.draw(E, B, S, D, dev))
+    if noise is None and trace == 'hutchinson':
+        noise = func.draw(steps * NF.CNF_STAGES[NF.CNF_METHODS[method]], B, S, D, dev)
+    seed = func.seed(dev) if trace == 'hutchinson' and not func.noise_on_cpu and func.noise_source is None else None
+    return NF.cnf_flow(z, ld, params, cfg, noise, noise_bwd, seed)
+
+
+odeint_adjoint = odeint
+
+
+class CNF(nn.Module):
+    """flows/cnf.py:124-173.  Same constructor, attributes, float64 field parameters and ``times`` buffer; ``forward`` integrates over
+    the flipped times, ``backward`` over the times as stored, each in one launch (functional.cnf_flow) with the adjoint gradient of
+    odeint.py:250-284.  ``backprop='normal'`` constructs and raises NotImplementedError when run.  ``noise`` / ``noise_bwd``: explicit
+    Hutchinson noise of the pass and of its backward pass, float32 (E, B, S, D) in evaluation order (tests)."""
+
+    def __init__(self, dims, times, solver_type, trace_estimator='hutchinson', backprop='adjoint', dtype=torch.float64,
+                 noise_on_cpu=False):
+        super().__init__()
+        assert backprop in ['normal', 'adjoint'], 'unsupported backprop type "%s"' % (backprop)
+        self.dims = dims
+        self.dtype = dtype
+        self.func = ODENet(dims, trace_estimator=trace_estimator, noise_on_cpu=noise_on_cpu).type(self.dtype)
+        self.method = solver_type
+        self.backprop = backprop
+        self.register_buffer('times', times.type(self.dtype))
+        self._sched = {}
+
+    @property
+    def noise_on_cpu(self):
+        return self.func.noise_on_cpu
+
+    @noise_on_cpu.setter
+    def noise_on_cpu(self, v):
+        self.func.noise_on_cpu = bool(v)
+
+    def _schedules(self, flipped, device):
+        """the packed device schedules of this direction and of its adjoint, rebuilt when ``times`` or the method changed"""
+        key = (bool(flipped), str(device))
+        tag = (self.times.data_ptr(), self.times._version, self.method)
+        hit = self._sched.get(key)
+        if hit is None or hit[0] != tag:
+            t = self.times.detach().cpu()
+            a, b = (torch.flip(t, dims=[0]), t) if flipped else (t, torch.flip(t, dims=[0]))
+            hit = self._sched[key] = (tag, NF.cnf_pack_schedule(a, self.method, device), NF.cnf_pack_schedule(b, self.method, device))
+        return hit[1], hit[2]
+
+    def _run(self, z, log_df_dz, flipped, noise, noise_bwd):
+        if not z.is_cuda:
+            N.ptr(z)                                                        # the engine's "no CPU path" error
+        if self.backprop == 'normal':
+            raise NotImplementedError('CNF(backprop="normal") is not served by the engine: the kernels implement the adjoint form '
+                                      '(flows/odeint.py:250-284), the only one Ffjord can select')
+        if self.dtype != torch.float64:
+            raise NotImplementedError('the CNF kernels integrate in float64 (the reference\'s default), got dtype=%s' % self.dtype)
+        func, dev = self.func, z.device
+        (sched, steps), (sched_rev, steps_rev) = self._schedules(flipped, dev)
+        trace, S = func.trace_mode()
+        B, D = z.shape[0], z.shape[-1]
+        cfg = (sched, steps, sched_rev, steps_rev, self.method, trace, S, lambda E: func.draw(E, B, S, D, dev))
+        seed = None
+        if trace == 'hutchinson':
+            if noise is None:
+                noise = func.draw(steps * NF.CNF_STAGES[NF.CNF_METHODS[self.method]], B, S, D, dev)
+            if not func.noise_on_cpu and func.noise_source is None:
+                seed = func.seed(dev)
+        return NF.cnf_flow(z, log_df_dz, func.field_params(), cfg, noise, noise_bwd, seed)
+
+    def forward(self, z, log_df_dz, noise=None, noise_bwd=None):
+        return self._run(z, log_df_dz, True, noise, noise_bwd)
+
+    def backward(self, z, log_df_dz, noise=None, noise_bwd=None):
+        return self._run(z, log_df_dz, False, noise, noise_bwd)
+
+
 def _param_shape(num_features):
     dims = [1] + [1 for _ in num_features]
     dims[1] = num_features[0]

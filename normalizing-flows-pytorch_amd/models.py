@@ -12,7 +12,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .layers import (ActNorm, AffineCoupling, AutoregressiveTransfrom, BatchNorm, Compose, InvertibleConv1x1, Logit,
+from .layers import (CNF, ActNorm, AffineCoupling, AutoregressiveTransfrom, BatchNorm, Compose, InvertibleConv1x1, Logit,
                      MixLogAttnCoupling, PlanarTransform, Squeeze2d, Unsqueeze2d)
 
 
@@ -207,6 +207,46 @@ class PlanarFlow(nn.Module):
     def _run(self, fn, z):
         if z.dim() != 2:
             raise RuntimeError('PlanarFlow takes (B, D) input, got shape %s' % (tuple(z.shape), ))
+        if z.is_cuda and z.device.index != torch.cuda.current_device():
+            with torch.cuda.device(z.device):
+                return fn(z, self._zero_ld(z))
+        return fn(z, self._zero_ld(z))
+
+    def forward(self, z):
+        return self._run(self.net, z)
+
+    def backward(self, z):
+        return self._run(self.net.backward, z)
+
+
+class Ffjord(nn.Module):
+    """flows/ffjord.py:10-42: ``cfg.layers`` x [ActNorm, CNF] on density data, the times ``linspace(t0, t1, steps)`` in float32 (stored
+    by each CNF as a float64 buffer of float32 values).  ``cfg.backprop`` is not forwarded, as in the reference: the CNFs use the
+    adjoint.  The reference builds an EMPTY flow for images (it constructs the NotImplementedError without raising it, ffjord.py:26);
+    this one raises.  ``cfg.noise_on_cpu`` (optional, default False) is handed to the CNFs: True reproduces the reference's CPU draws.
+    The model mixes float32 (ActNorm) and float64 (field) parameters: it trains with the reference's own loop (torch.optim.Adam,
+    main.py:78-92), not with FlowTrainer, whose gradient bucket is single-dtype."""
+
+    def __init__(self, dims, datatype=None, cfg=None):
+        super().__init__()
+        self.dims = dims
+        self.n_layers = cfg.layers
+        self.stepsize = cfg.stepsize
+        t0, t1 = cfg.t0, cfg.t1
+        steps = int(np.ceil((t1 - t0) / self.stepsize)) + 1
+        times = torch.linspace(t0, t1, steps, dtype=torch.float32)
+        if datatype == 'image':
+            raise NotImplementedError('Sorry, FFJORD for image generation is not supported!')
+        layers = []
+        for _ in range(self.n_layers):
+            layers.append(ActNorm(dims))
+            layers.append(CNF(dims, times=times, solver_type=cfg.solver, trace_estimator=cfg.trace,
+                              noise_on_cpu=getattr(cfg, 'noise_on_cpu', False)))
+        self.net = Compose(layers)
+
+    _zero_ld = _FlowModel._zero_ld
+
+    def _run(self, fn, z):
         if z.is_cuda and z.device.index != torch.cuda.current_device():
             with torch.cuda.device(z.device):
                 return fn(z, self._zero_ld(z))
