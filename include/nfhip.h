@@ -1142,8 +1142,9 @@ int nf_flowpp_img_pre_bwd(const float* x, const float* a, const float* ln1_g, co
                           const float* gt_part, float* g_x, float* g_a, float* g_ln1_g, float* g_ln1_b, float* g_pos, int per_sample,
                           int64_t B, int H, int W, nf_stream_t stream);
 
-/* ---- on-device synthetic batches (csrc/datagen.hip)  flows/dataset.py:13-34, :120; replaces the per-step H2D copy main.py:79 --
- * kind 0 moons, 1 circles, 2 normals: out (n, 2), per_sample = 2;  3 cifar-like uniform uint8 / 255: out (n, per_sample).
+/* ---- on-device synthetic batches (csrc/datagen.hip)  flows/dataset.py:13-50, :120; replaces the per-step H2D copy main.py:79 --
+ * kind 0 moons, 1 circles, 2 normals: out (n, 2), per_sample = 2;  3 cifar-like uniform uint8 / 255: out (n, per_sample);
+ * kind 4 swiss, 5 s_curve (dataset.py:37-50): out (n, 3), per_sample = 3.
  * Counter-based Philox4x32-10 keyed by (seed, *step, sample): stateless and reproducible; `step` (device int64, NULL = 0) is read
  * by the kernel, so a captured graph draws a fresh batch per replay once nf_sample_advance (step += 1) follows it.             */
 int nf_sample_data(int kind, float* out, int64_t n, int per_sample, int64_t seed, const int64_t* step, nf_stream_t stream);
@@ -1162,6 +1163,18 @@ int nf_nll_loss_bwd(const float* z, const float* g_loss, float* g_z, float* g_ld
 int nf_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int* step, const float* lr,
                  float beta1, float beta2, float eps, float weight_decay, float grad_scale, int64_t n,
                  nf_stream_t stream);
+
+/* ---- fused RMSprop over flat buffers (torch.optim.RMSprop with momentum 0, not centred: main.py:56-59) ----------------
+ * step[0] += 1 (device int32), then for every i < n:  g = grad[i]*grad_scale + wd*p ; v = alpha v + (1-alpha) g^2 ;
+ * p -= lr[0] * g / (sqrt(v) + eps).  One launch over the flat buffers (float4 where they are 16-byte aligned).       */
+int nf_rmsprop_step(float* param, const float* grad, float* square_avg, int* step, const float* lr, float alpha, float eps,
+                    float weight_decay, float grad_scale, int64_t n, nf_stream_t stream);
+
+/* ---- StepLR on the device (torch.optim.lr_scheduler.StepLR stepped after every optim.step(): main.py:68-70, :90) -----
+ * one thread: lr[0] = (float)(base_lr[0] * decay_ratio ^ (pos[0] / decay_steps)), then pos[0] += 1.  Enqueued before the
+ * optimizer launch of the step it belongs to; all three words are device memory, so a captured hipGraph decays on replay.
+ * pos is the schedule's own counter (restarted by a checkpoint load), not Adam's bias-correction step.                  */
+int nf_lr_step_decay(float* lr, const double* base_lr, int* pos, int decay_steps, double decay_ratio, nf_stream_t stream);
 
 /* dst_k[0:n_k] = src_k[0:n_k] for up to NF_COPY_MAX tensors in one launch (gradient gather into the flat bucket)   */
 #define NF_COPY_MAX 128

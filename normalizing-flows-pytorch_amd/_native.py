@@ -23,7 +23,7 @@ OP_ACTNORM, OP_FLOWBN = 0, 1
 
 _P, _I, _L, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 _CTYPES = {'const float*': _P, 'float*': _P, 'int*': _P, 'char*': _P, 'nf_stream_t': _P, 'int': _I, 'int64_t': _L,
-           'float': _F}
+           'float': _F, 'double': ctypes.c_double}
 
 _lib = None
 

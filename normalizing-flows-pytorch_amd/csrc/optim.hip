@@ -5,6 +5,7 @@
 //   g += wd * p ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ;
 //   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // `step` and `lr` live in device memory so that a captured hipGraph replays with the right values.
+// Below it: the same for RMSprop (nf_rmsprop_step) and the StepLR schedule as a one-thread launch (nf_lr_step_decay).
 #include "nf_common.h"
 
 __global__ void k_adam_tick(int* __restrict__ step) { step[0] += 1; }
@@ -40,6 +41,100 @@ extern "C" int nf_adam_step(float* param, const float* grad, float* exp_avg, flo
     NF_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_adam_step, dim3(nf_grid_for(n)), dim3(NF_BLOCK), 0, st, param, grad, exp_avg, exp_avg_sq, step, lr,
                        beta1, beta2, eps, weight_decay, grad_scale, n);
+    NF_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Fused RMSprop over the same flat buffers: torch.optim.RMSprop with momentum = 0 and centered = False, the only form the
+// reference constructs (main.py:56-59):
+//   g += wd * p ; v = alpha v + (1 - alpha) g^2 ; p -= lr * g / (sqrt(v) + eps)
+// A pure stream, 12 B read and 8 B written per element.  Where the three flat buffers and the gradient are 16-byte aligned the
+// body moves float4s (VEC) and the last n % 4 elements take the scalar form in the same launch; otherwise every element does.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void nf_rmsprop_one(float& p, float g, float& v, float lr, float alpha, float eps, float wd,
+                                               float grad_scale) {
+    float gi = g * grad_scale;
+    if (wd != 0.f) gi = fmaf(wd, p, gi);
+    v = fmaf(alpha, v, (1.f - alpha) * gi * gi);
+    p = p - lr * (gi / (sqrtf(v) + eps));
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(NF_BLOCK) k_rmsprop_step(float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ v, const float* __restrict__ lr_ptr, float alpha,
+                                                           float eps, float wd, float grad_scale, int64_t n) {
+    const float lr = lr_ptr[0];
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, gstride = (int64_t)gridDim.x * blockDim.x;
+    int64_t done = 0;                                     // elements [0, done) are covered by the float4 body
+    if (VEC) {
+        const int64_t n4 = n / 4;
+        float4* __restrict__ p4 = reinterpret_cast<float4*>(p);
+        float4* __restrict__ v4 = reinterpret_cast<float4*>(v);
+        const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
+        for (int64_t i = tid; i < n4; i += gstride) {
+            float4 pi = p4[i], vi = v4[i];
+            const float4 gi = g4[i];
+            nf_rmsprop_one(pi.x, gi.x, vi.x, lr, alpha, eps, wd, grad_scale);
+            nf_rmsprop_one(pi.y, gi.y, vi.y, lr, alpha, eps, wd, grad_scale);
+            nf_rmsprop_one(pi.z, gi.z, vi.z, lr, alpha, eps, wd, grad_scale);
+            nf_rmsprop_one(pi.w, gi.w, vi.w, lr, alpha, eps, wd, grad_scale);
+            v4[i] = vi;
+            p4[i] = pi;
+        }
+        done = 4 * n4;
+    }
+    for (int64_t i = done + tid; i < n; i += gstride) {
+        float pi = p[i], vi = v[i];
+        nf_rmsprop_one(pi, g[i], vi, lr, alpha, eps, wd, grad_scale);
+        v[i] = vi;
+        p[i] = pi;
+    }
+}
+
+extern "C" int nf_rmsprop_step(float* param, const float* grad, float* square_avg, int* step, const float* lr, float alpha,
+                               float eps, float weight_decay, float grad_scale, int64_t n, nf_stream_t stream) {
+    if (n < 0) return NF_E_BADARG;
+    if (n == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(1), 0, st, step);
+    NF_CHECK_LAUNCH();
+    const bool vec = n >= 4 && (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)square_avg) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(k_rmsprop_step<true>, dim3(nf_grid_for(n / 4)), dim3(NF_BLOCK), 0, st, param, grad, square_avg, lr, alpha,
+                           eps, weight_decay, grad_scale, n);
+    else
+        hipLaunchKernelGGL(k_rmsprop_step<false>, dim3(nf_grid_for(n)), dim3(NF_BLOCK), 0, st, param, grad, square_avg, lr, alpha,
+                           eps, weight_decay, grad_scale, n);
+    NF_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// StepLR on the device (main.py:68-70, :90: scheduler.step() after every optim.step()): one thread, enqueued BEFORE the
+// optimizer launch of the same step, so that it is part of the captured graph and replays decay without host work.
+// pos[0] counts the optimizer steps taken under the schedule; step number pos + 1 trains at
+//   lr = base_lr * decay_ratio ^ (pos / decay_steps)
+// formed in double from the base rate and the INTEGER exponent (repeated squaring) and rounded to float once -- multiplying
+// a float by the ratio at every boundary would drift from torch's double-precision StepLR.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ void k_lr_step_decay(float* __restrict__ lr, const double* __restrict__ base_lr, int* __restrict__ pos, int decay_steps,
+                                double decay_ratio) {
+    const int t = pos[0];
+    int e = t / decay_steps;
+    double f = 1.0, b = decay_ratio;
+    while (e > 0) {
+        if (e & 1) f *= b;
+        b *= b;
+        e >>= 1;
+    }
+    lr[0] = (float)(base_lr[0] * f);
+    pos[0] = t + 1;
+}
+
+extern "C" int nf_lr_step_decay(float* lr, const double* base_lr, int* pos, int decay_steps, double decay_ratio, nf_stream_t stream) {
+    if (lr == nullptr || base_lr == nullptr || pos == nullptr || decay_steps < 1) return NF_E_BADARG;
+    hipLaunchKernelGGL(k_lr_step_decay, dim3(1), dim3(1), 0, (hipStream_t)stream, lr, base_lr, pos, decay_steps, decay_ratio);
     NF_CHECK_LAUNCH();
     return 0;
 }

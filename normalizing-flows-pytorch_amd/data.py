@@ -1,7 +1,8 @@
 """
 Seeded synthetic inputs of the benchmark configurations.  The reference's data code (flows/dataset.py) needs
 hydra / torchvision / sklearn tables and cannot travel; these are numpy restatements of the same distributions that
-take the sample count ``n`` directly (flows/dataset.py:13-34; sklearn.datasets.make_moons / make_circles geometry).
+take the sample count ``n`` directly (flows/dataset.py:13-50; sklearn.datasets.make_moons / make_circles / make_swiss_roll /
+make_s_curve geometry).
 """
 import numpy as np
 import torch
@@ -49,7 +50,25 @@ def cifar_like(n, rng, dims=(3, 32, 32)):
     return (rng.integers(0, 256, size=(n, ) + tuple(dims), dtype=np.uint8).astype(np.float32) / 255.0)
 
 
-GENERATORS = {'moons': moons, 'circles': circles, 'normals': normals, 'cifar': cifar_like}
+def swiss(n, rng, noise=0.08):
+    """sklearn make_swiss_roll: t = 1.5 pi (1 + 2u), (t cos t, 21 u2, t sin t) + gaussian noise, then x * 0.07, y * 0.07 - 1,
+    z * 0.07   (dataset.py:37-42)"""
+    t = 1.5 * np.pi * (1.0 + 2.0 * rng.random(n))
+    pts = np.stack([t * np.cos(t), 21.0 * rng.random(n), t * np.sin(t)], axis=1)
+    pts = pts + rng.normal(scale=noise, size=pts.shape)
+    return (pts * 0.07 - np.array([0.0, 1.0, 0.0])).astype(np.float32)
+
+
+def s_curve(n, rng, noise=0.08):
+    """sklearn make_s_curve: t = 3 pi (u - 1/2), (sin t, 2 u2, sign(t) (cos t - 1)) + gaussian noise, then x * 0.7, (y - 1) * 0.7,
+    z * 0.35   (dataset.py:45-50)"""
+    t = 3.0 * np.pi * (rng.random(n) - 0.5)
+    pts = np.stack([np.sin(t), 2.0 * rng.random(n), np.sign(t) * (np.cos(t) - 1.0)], axis=1)
+    pts = pts + rng.normal(scale=noise, size=pts.shape)
+    return ((pts - np.array([0.0, 1.0, 0.0])) * np.array([0.7, 0.7, 0.35])).astype(np.float32)
+
+
+GENERATORS = {'moons': moons, 'circles': circles, 'normals': normals, 'cifar': cifar_like, 'swiss': swiss, 's_curve': s_curve}
 
 
 def sample(name, n, seed):
@@ -57,7 +76,7 @@ def sample(name, n, seed):
 
 
 # ---- on-device generation (csrc/datagen.hip): same distributions, drawn where they are consumed --------------------------------------
-KINDS = {'moons': 0, 'circles': 1, 'normals': 2, 'cifar': 3}
+KINDS = {'moons': 0, 'circles': 1, 'normals': 2, 'cifar': 3, 'swiss': 4, 's_curve': 5}
 
 
 class DeviceSampler:
@@ -80,7 +99,10 @@ class DeviceSampler:
         per = 1
         for d_ in self.dims:
             per *= int(d_)
-        if self.kind != 3 and per != 2:
+        if self.kind in (4, 5):
+            if self.dims != (3, ):
+                raise ValueError('%s is a 3-D data set' % name)
+        elif self.kind != 3 and per != 2:
             raise ValueError('%s is a 2-D data set' % name)
         self.per = per
         if rank is None:

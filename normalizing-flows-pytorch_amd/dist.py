@@ -57,7 +57,11 @@ class GradBucket:
     returning a temporary that costs one extra add launch per parameter."""
 
     def __init__(self, params, process_group=None, flatten_params=False):
+        params = list(params)
         self.params = [p for p in params if p.requires_grad]
+        # position of every bucketed parameter in the iterable it came from (net.parameters()): how torch.optim keys its state
+        self.index = [i for i, p in enumerate(params) if p.requires_grad]
+        self.n_all = len(params)
         if not self.params:
             raise ValueError('no trainable parameters')
         dev, dt = self.params[0].device, self.params[0].dtype

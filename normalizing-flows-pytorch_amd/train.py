@@ -35,45 +35,226 @@ def bits_per_dim(loss, dims):
     return float(loss) / (D * math.log(2.0))
 
 
-class FlatAdam:
-    """torch.optim.Adam semantics (the reference's optimizer, main.py:56-64) as ONE fused HIP launch over the flat
-    parameter / gradient buffers of a GradBucket.  ``lr`` and the step counter live on the device, so a captured
-    hipGraph keeps working when a scheduler changes the rate (``set_lr``)."""
+class _FlatOptimizer:
+    """What FlatAdam and FlatRMSprop share: ONE fused HIP launch over the flat parameter / gradient buffers of a GradBucket, with
+    ``lr`` and the step counter on the device, so that a captured hipGraph keeps working when the rate changes (``set_lr``).
 
-    def __init__(self, bucket, lr=1.0e-4, betas=(0.9, 0.999), eps=1.0e-8, weight_decay=0.0):
+    ``decay_steps`` (None: no schedule, no extra launch) puts torch's StepLR on the device (nf_lr_step_decay, one thread, enqueued
+    in front of the optimizer launch and therefore part of a captured step): optimizer step t = 1, 2, ... since construction or the
+    last checkpoint load runs at ``base_lr * decay_ratio ** ((t - 1) // decay_steps)``, the rate StepLR gives when scheduler.step()
+    follows optim.step() (main.py:89-90).  ``sched_pos`` counts those steps; it is NOT ``step_count``, which a checkpoint carries on
+    (Adam's bias correction) while the reference's schedule restarts at every load.  ``lr`` holds the rate in use."""
+
+    KIND = None                     # 'Adam' / 'RMSprop': the torch.optim class whose state_dict format torch_state_dict() speaks
+    MOMENTS = ()                    # names of the per-parameter moment buffers, as torch.optim names them
+
+    def _init_common(self, bucket, lr, decay_steps, decay_ratio):
         if bucket.flat_params is None:
-            raise ValueError('FlatAdam needs GradBucket(..., flatten_params=True)')
+            raise ValueError('%s needs GradBucket(..., flatten_params=True)' % type(self).__name__)
         from . import _native as N
         self._N = N
         self.bucket = bucket
-        self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
         dev = bucket.flat.device
-        self.exp_avg = torch.zeros_like(bucket.flat)
-        self.exp_avg_sq = torch.zeros_like(bucket.flat)
+        for k in self.MOMENTS:
+            setattr(self, k, torch.zeros_like(bucket.flat))
         self.step_count = torch.zeros(1, dtype=torch.int32, device=dev)
         self.lr = torch.full((1, ), float(lr), dtype=torch.float32, device=dev)
+        self._lr_host = float(lr)   # the rate as the caller gave it (a double): what a checkpoint records while ``lr`` still rounds to it
+        self.decay_steps = None if decay_steps is None else int(decay_steps)
+        self.decay_ratio = float(decay_ratio)
+        if self.decay_steps is not None:
+            if self.decay_steps < 1:
+                raise ValueError('decay_steps must be a positive number of optimizer steps, got %r' % (decay_steps, ))
+            self.base_lr = torch.full((1, ), float(lr), dtype=torch.float64, device=dev)
+            self.sched_pos = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def set_lr(self, lr):
+        """the rate of a trainer without a schedule, the BASE rate of one with a schedule"""
         self.lr.fill_(float(lr))
+        self._lr_host = float(lr)
+        if self.decay_steps is not None:
+            self.base_lr.fill_(float(lr))
+            self.lr.fill_(self.scheduled_lr(float(lr), int(self.sched_pos.item())))
 
-    def step(self):
-        N, b = self._N, self.bucket
+    def scheduled_lr(self, base, pos):
+        """host restatement of nf_lr_step_decay: the rate of the step that follows ``pos`` completed ones"""
+        return float(base) * self.decay_ratio ** (int(pos) // self.decay_steps)
+
+    def set_schedule(self, base_lr, pos):
+        """restart (pos = 0) or reposition the schedule; the state a captured graph reads is rewritten in place"""
+        self.base_lr.fill_(float(base_lr))
+        self.sched_pos.fill_(int(pos))
+        self.lr.fill_(self.scheduled_lr(base_lr, pos))
+
+    def _check_homed(self):
         # the parameters must still live in the flat buffer (net.to() / .cpu() after construction re-homes p.data silently)
+        b = self.bucket
         p0, p1 = b.params[0], b.params[-1]
         if (p0.data_ptr() != b.flat_params.data_ptr()
                 or p1.data_ptr() + p1.numel() * 4 != b.flat_params.data_ptr() + b.numel * 4):
-            raise RuntimeError('FlatAdam: the parameters no longer live in the GradBucket\'s flat buffer (was the model moved '
-                               'with .to() / .cpu() after the trainer was built?); build a new FlowTrainer')
-        N.call('nf_adam_step', N.ptr(b.flat_params), N.ptr(b.flat), N.ptr(self.exp_avg), N.ptr(self.exp_avg_sq),
-               N.ptr(self.step_count), N.ptr(self.lr), self.betas[0], self.betas[1], self.eps, self.weight_decay, 1.0,
-               b.numel, N.stream())
+            raise RuntimeError('%s: the parameters no longer live in the GradBucket\'s flat buffer (was the model moved '
+                               'with .to() / .cpu() after the trainer was built?); build a new FlowTrainer' % type(self).__name__)
 
+    def step(self):
+        N = self._N
+        self._check_homed()
+        if self.decay_steps is not None:
+            N.call('nf_lr_step_decay', N.ptr(self.lr), N.ptr(self.base_lr, (torch.float64, )), N.ptr(self.sched_pos),
+                   self.decay_steps, self.decay_ratio, N.stream())
+        self._launch()
+
+    # -- the private flat format (unchanged) ---------------------------------------------------------------------------------------
     def state_dict(self):
-        return {'exp_avg': self.exp_avg, 'exp_avg_sq': self.exp_avg_sq, 'step': self.step_count, 'lr': self.lr}
+        sd = {k: getattr(self, k) for k in self.MOMENTS}
+        sd.update({'step': self.step_count, 'lr': self.lr})
+        return sd
 
     def load_state_dict(self, sd):
         for k, t in self.state_dict().items():
             t.copy_(sd[k])
+
+    # -- torch.optim's format: what the reference's checkpoints hold (main.py:94-107) -----------------------------------------------
+    def _hyper(self):
+        raise NotImplementedError
+
+    def _torch_group(self, lr):
+        """param_groups[0] as the installed torch.optim class of the same hyper-parameters writes it (whatever keys that version
+        carries), taken from a throw-away instance over one scalar"""
+        cls = getattr(torch.optim, self.KIND)
+        group = dict(cls([torch.nn.Parameter(torch.zeros(1))], lr=float(lr), **self._hyper()).state_dict()['param_groups'][0])
+        return group
+
+    def torch_state_dict(self):
+        """the optimizer state in ``torch.optim.<KIND>.state_dict()`` format: ``state[i]`` keyed by the parameter's position in the
+        iterable the bucket was built from (``net.parameters()``; frozen parameters hold a position and no state, as in torch),
+        per-parameter ``step`` and moments shaped like the parameter (copies: the flat buffers stay where they are).  An optimizer
+        that never stepped has no state entries, like torch's."""
+        b = self.bucket
+        step = int(self.step_count.item())
+        state = {}
+        if step > 0:
+            o = 0
+            for i, p in zip(b.index, b.params):
+                n = p.numel()
+                e = {'step': torch.tensor(float(step), dtype=torch.float32)}
+                for k in self.MOMENTS:
+                    e[k] = getattr(self, k)[o:o + n].view_as(p).clone()
+                state[i] = e
+                o += n
+        lr = float(self.lr.item())
+        if float(torch.tensor(self._lr_host, dtype=torch.float32)) == lr:
+            lr = self._lr_host
+        if self.decay_steps is not None:                            # torch's group holds the rate of the NEXT step after scheduler.step()
+            lr = self.scheduled_lr(self.base_lr.item(), self.sched_pos.item())
+        group = self._torch_group(lr)
+        if self.decay_steps is not None:
+            group['initial_lr'] = float(self.base_lr.item())        # (the key a torch scheduler adds to the group)
+        group['params'] = list(range(b.n_all))
+        return {'state': state, 'param_groups': [group]}
+
+    def load_torch_state_dict(self, sd):
+        """the reverse: moments and step into the flat buffers (in place, a captured graph goes on reading them), ``lr`` from the
+        group.  The other hyper-parameters are launch arguments, frozen into a captured graph: they must equal this optimizer's.
+        A schedule, if any, restarts at position 0 from the loaded rate, as the reference's does after load_ckpt."""
+        groups = sd['param_groups']
+        if len(groups) != 1:
+            raise ValueError('%s holds one parameter group, the state dict has %d' % (type(self).__name__, len(groups)))
+        group, b = groups[0], self.bucket
+        if len(group['params']) != b.n_all:
+            raise ValueError('the state dict covers %d parameters, the model has %d' % (len(group['params']), b.n_all))
+        for k, mine in self._hyper().items():
+            theirs = group.get(k, mine)
+            theirs = tuple(float(x) for x in theirs) if isinstance(theirs, (tuple, list)) else float(theirs)
+            mine = tuple(float(x) for x in mine) if isinstance(mine, (tuple, list)) else float(mine)
+            if theirs != mine:
+                raise ValueError('%s was built with %s = %r, the state dict was written with %r; build the optimizer with the '
+                                 'checkpoint\'s hyper-parameters' % (type(self).__name__, k, mine, theirs))
+        for k in ('amsgrad', 'centered', 'maximize'):
+            if group.get(k, False):
+                raise ValueError('%s does not implement %s=True' % (type(self).__name__, k))
+        if float(group.get('momentum', 0.0)) != 0.0:
+            raise ValueError('%s does not implement momentum' % type(self).__name__)
+        where = {pid: j for j, pid in enumerate(group['params'])}      # torch keys the state by the ids listed in the group
+        state = {where[k]: v for k, v in sd['state'].items()}
+        steps = {int(float(e['step'])) for e in state.values()}
+        if len(steps) > 1:
+            raise ValueError('per-parameter step counts differ (%s): one fused launch keeps one counter' % sorted(steps))
+        with torch.no_grad():
+            o = 0
+            for i, p in zip(b.index, b.params):
+                n = p.numel()
+                e = state.get(i)
+                for k in self.MOMENTS:
+                    dst = getattr(self, k)[o:o + n]
+                    if e is None:                           # torch keeps no state for a parameter that never saw a gradient
+                        dst.zero_()
+                    else:
+                        dst.copy_(e[k].reshape(-1))
+                o += n
+            self.step_count.fill_(steps.pop() if steps else 0)
+            lr = float(group['lr'])
+            self.lr.fill_(lr)
+            self._lr_host = lr
+            if self.decay_steps is not None:
+                self.set_schedule(lr, 0)
+
+
+class FlatAdam(_FlatOptimizer):
+    """torch.optim.Adam semantics (the reference's optimizer, main.py:56-64) as ONE fused HIP launch over the flat
+    parameter / gradient buffers of a GradBucket.  ``lr`` and the step counter live on the device, so a captured
+    hipGraph keeps working when a scheduler changes the rate (``set_lr``, or the on-device StepLR of ``decay_steps``)."""
+
+    KIND, MOMENTS = 'Adam', ('exp_avg', 'exp_avg_sq')
+
+    def __init__(self, bucket, lr=1.0e-4, betas=(0.9, 0.999), eps=1.0e-8, weight_decay=0.0, decay_steps=None, decay_ratio=0.5):
+        self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
+        self._init_common(bucket, lr, decay_steps, decay_ratio)
+
+    def _hyper(self):
+        return {'betas': (float(self.betas[0]), float(self.betas[1])), 'eps': self.eps, 'weight_decay': self.weight_decay}
+
+    def _launch(self):
+        N, b = self._N, self.bucket
+        N.call('nf_adam_step', N.ptr(b.flat_params), N.ptr(b.flat), N.ptr(self.exp_avg), N.ptr(self.exp_avg_sq),
+               N.ptr(self.step_count), N.ptr(self.lr), self.betas[0], self.betas[1], self.eps, self.weight_decay, 1.0,
+               b.numel, N.stream())
+
+
+class FlatRMSprop(_FlatOptimizer):
+    """torch.optim.RMSprop with momentum 0 and centered False -- the form the reference constructs (main.py:56-59) -- as one fused
+    HIP launch (nf_rmsprop_step) over the flat buffers; same surface as FlatAdam."""
+
+    KIND, MOMENTS = 'RMSprop', ('square_avg', )
+
+    def __init__(self, bucket, lr=1.0e-2, alpha=0.99, eps=1.0e-8, weight_decay=0.0, decay_steps=None, decay_ratio=0.5):
+        self.alpha, self.eps, self.weight_decay = alpha, eps, weight_decay
+        self._init_common(bucket, lr, decay_steps, decay_ratio)
+
+    def _hyper(self):
+        return {'alpha': self.alpha, 'eps': self.eps, 'weight_decay': self.weight_decay}
+
+    def _launch(self):
+        N, b = self._N, self.bucket
+        N.call('nf_rmsprop_step', N.ptr(b.flat_params), N.ptr(b.flat), N.ptr(self.square_avg), N.ptr(self.step_count),
+               N.ptr(self.lr), self.alpha, self.eps, self.weight_decay, 1.0, b.numel, N.stream())
+
+
+def _to_reference_layout(sd, bucket):
+    """a torch.optim state dict over ``bucket.params`` (the trainable parameters only) re-keyed by position in net.parameters(),
+    the layout of the reference's ``torch.optim.X(net.parameters())`` (main.py:57-64)"""
+    group = dict(sd['param_groups'][0])
+    group['params'] = list(range(bucket.n_all))
+    group['lr'] = float(group['lr'])                    # (a device tensor under a captured framework optimizer)
+    return {'state': {bucket.index[k]: v for k, v in sd['state'].items()}, 'param_groups': [group]}
+
+
+def _from_reference_layout(sd, bucket):
+    group = dict(sd['param_groups'][0])
+    if len(group['params']) != bucket.n_all:
+        raise ValueError('the state dict covers %d parameters, the model has %d' % (len(group['params']), bucket.n_all))
+    back = {i: k for k, i in enumerate(bucket.index)}
+    group['params'] = list(range(len(bucket.params)))
+    return {'state': {back[i]: v for i, v in sd['state'].items() if i in back}, 'param_groups': [group]}
 
 
 class _HipStepGraph:
@@ -94,7 +275,10 @@ class _HipStepGraph:
 
 
 class FlowTrainer:
-    """Adam (lr 1e-4, betas (0.9, 0.999): configs/default.yaml:13-20) on the NLL, gradients in one flat bucket.
+    """Adam (lr 1e-4, betas (0.9, 0.999): configs/default.yaml:13-20) or RMSprop (``optimizer='rmsprop'``, main.py:56-59) on the
+    NLL, gradients in one flat bucket.  ``decay_steps`` / ``decay_ratio``: the reference's StepLR (main.py:68-70, :90), on the device
+    and inside the captured step with the fused optimizers, torch.optim.lr_scheduler.StepLR on the torch.optim path (CPU, or
+    ``fused_adam=False``).  ``save_ckpt`` / ``load_ckpt`` speak the reference's checkpoint format (main.py:94-107).
 
     ``graph=True`` captures zero-grad + forward + backward into one hipGraph and the optimizer step into a second one
     (the gradient all-reduce runs between the two replays; a single process captures both into ONE graph), after
@@ -104,7 +288,10 @@ class FlowTrainer:
     TRAIN_MODE_RECHECK = 256        # calls of train_on_batch between two walks over the submodules' training flags
 
     def __init__(self, net, lr=1.0e-4, betas=(0.9, 0.999), weight_decay=0.0, graph=False, warmup=3, process_group=None,
-                 fused_adam=True, sampler=None, sync_stats=False, graph_factory=None, one_graph=None):
+                 fused_adam=True, sampler=None, sync_stats=False, graph_factory=None, one_graph=None, optimizer='adam',
+                 decay_steps=None, decay_ratio=0.5):
+        if optimizer not in ('adam', 'rmsprop'):
+            raise Exception('optimizer "%s" is currently not supported' % (optimizer, ))       # (the reference's words, main.py:66)
         self.net = net
         self.one_graph = (os.environ.get('NF_DP_ONE_GRAPH', '0') == '1') if one_graph is None else bool(one_graph)
         self._g_whole = False
@@ -123,11 +310,30 @@ class FlowTrainer:
         self.bucket = nfdist.GradBucket(net.parameters(), process_group, flatten_params=fused_adam)
         self.graph = bool(graph)
         self._graph_factory = graph_factory or _HipStepGraph
+        self.decay_steps = None if decay_steps is None else int(decay_steps)
+        self.decay_ratio = float(decay_ratio)
+        self._base_lr = float(lr)
+        self._sched = None          # the torch.optim path's StepLR (host side, stepped after every optimizer step or replay)
         if fused_adam:
-            self.optim = FlatAdam(self.bucket, lr=lr, betas=betas, weight_decay=weight_decay)
+            if optimizer == 'adam':
+                self.optim = FlatAdam(self.bucket, lr=lr, betas=betas, weight_decay=weight_decay, decay_steps=decay_steps,
+                                      decay_ratio=decay_ratio)
+            else:
+                self.optim = FlatRMSprop(self.bucket, lr=lr, weight_decay=weight_decay, decay_steps=decay_steps,
+                                         decay_ratio=decay_ratio)
         else:
-            self.optim = torch.optim.Adam(self.bucket.params, lr=lr, betas=betas, weight_decay=weight_decay,
-                                          capturable=self.graph and on_gpu, foreach=True)
+            capturable = self.graph and on_gpu
+            if capturable and decay_steps is not None:
+                # a captured framework optimizer reads a python-float rate once, at capture: the scheduler needs a device tensor to fill
+                lr = torch.tensor(float(lr), dtype=torch.float32, device=next(net.parameters()).device)
+            if optimizer == 'adam':
+                self.optim = torch.optim.Adam(self.bucket.params, lr=lr, betas=betas, weight_decay=weight_decay,
+                                              capturable=capturable, foreach=True)
+            else:
+                self.optim = torch.optim.RMSprop(self.bucket.params, lr=lr, weight_decay=weight_decay, capturable=capturable,
+                                                 foreach=True)
+            if decay_steps is not None:
+                self._sched = torch.optim.lr_scheduler.StepLR(self.optim, step_size=self.decay_steps, gamma=self.decay_ratio)
         self.warmup = warmup
         self._eager_steps = 0
         self._replicas_synced = False
@@ -211,6 +417,13 @@ class FlowTrainer:
             arr = (CopyDesc * len(chunk))(*[CopyDesc(g.data_ptr(), v.data_ptr(), g.numel()) for g, v in chunk])
             N.call('nf_multi_copy', ctypes.addressof(arr), len(chunk), N.stream())
 
+    def _optim_step(self):
+        """one eager optimizer step.  The fused optimizers carry their schedule inside ``step()``; the torch.optim path's StepLR is
+        host code and follows it here -- and every graph replay in train_on_batch, never inside a capture."""
+        self.optim.step()
+        if self._sched is not None:
+            self._sched.step()
+
     def _capture(self, y):
         self._static_y = y.clone() if y is not None else None
         if torch.cuda.is_available() and (y is None or y.is_cuda):
@@ -219,13 +432,13 @@ class FlowTrainer:
             with torch.cuda.stream(side):               # one more eager step on the side stream (capture etiquette)
                 self._forward_backward(self._static_y)
                 self.bucket.all_reduce_mean_()
-                self.optim.step()
+                self._optim_step()
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
         else:                                           # (a CPU stand-in graph factory: the same extra eager step, no streams)
             self._forward_backward(self._static_y)
             self.bucket.all_reduce_mean_()
-            self.optim.step()
+            self._optim_step()
         single = not self.bucket.collective            # no all-reduce between backward and Adam: one graph, one replay
         # N > 1 with one_graph: the flat bucket's all-reduce is captured BETWEEN backward and Adam (ProcessGroupNCCL enqueues the RCCL
         # kernel on the capturing stream): one replay per step instead of two graph launches and an eager collective in between.
@@ -282,8 +495,13 @@ class FlowTrainer:
         # step takes on the device.  The root's flag answers for the tree on most calls; a CHILD put into eval() on its own (the root stays
         # in training mode) is found by a walk on the first call and every TRAIN_MODE_RECHECK calls after it
         self._calls_since_mode_walk += 1
-        if not self.net.training or self._calls_since_mode_walk >= self.TRAIN_MODE_RECHECK:
-            if not self.net.training or any(not m_.training for m_ in self.net.modules()):
+        if not self.net.training:
+            # the state log_py() / sample_y() / net.eval() leave (main.py alternates train() and eval() at every report, :73-76, :327):
+            # Module.train() puts the whole tree back, graph or no graph -- a replay launches what was captured whatever the flags say
+            self.net.train()
+            self._calls_since_mode_walk = 0
+        elif self._calls_since_mode_walk >= self.TRAIN_MODE_RECHECK:
+            if any(not m_.training for m_ in self.net.modules()):
                 if self._g_fb is not None:
                     raise RuntimeError('FlowTrainer: a submodule was switched to eval() after the step was captured in a hipGraph (the graph '
                                        'replays training-mode launches); build a new FlowTrainer')
@@ -311,10 +529,12 @@ class FlowTrainer:
             if self._g_opt is not None:
                 self.bucket.all_reduce_mean_()
                 self._g_opt.replay()
+            if self._sched is not None:
+                self._sched.step()
             return self._static_z, self._static_loss
         z, loss = self._forward_backward(y)
         self.bucket.all_reduce_mean_()
-        self.optim.step()
+        self._optim_step()
         self._eager_steps += 1
         if not self._replicas_synced:
             self._sync_replicas_after_first_step()
@@ -330,6 +550,68 @@ class FlowTrainer:
             # every parameter AND buffer: the frozen PLU constants (P, pivots, sign_s), MAF's perm and the running statistics
             # too, so that replicas built from different seeds cannot keep private copies of those
             nfdist.broadcast_parameters(self.net, src=0, group=self.bucket.group, force=True)
+
+    # -- the reference's configuration and checkpoints ------------------------------------------------------------------------------
+    @classmethod
+    def from_cfg(cls, net, cfg, **kw):
+        """``cfg``: the reference's ``cfg.optimizer`` node (configs/default.yaml: name, lr, beta1, beta2, weight_decay, decay_steps,
+        decay_ratio), read as main.py:56-70 reads it; ``kw`` goes to the constructor (graph, sampler, ...)."""
+        return cls(net, lr=cfg.lr, betas=(cfg.beta1, cfg.beta2), weight_decay=cfg.weight_decay, optimizer=cfg.name,
+                   decay_steps=cfg.decay_steps, decay_ratio=cfg.decay_ratio, **kw)
+
+    @property
+    def _fused(self):
+        return isinstance(self.optim, _FlatOptimizer)
+
+    def current_lr(self):
+        """the rate the next optimizer step runs at (synchronises on the fused path)"""
+        if self._fused:
+            o = self.optim
+            return float(o.lr.item()) if o.decay_steps is None else o.scheduled_lr(o.base_lr.item(), o.sched_pos.item())
+        return float(self.optim.param_groups[0]['lr'])
+
+    def save_ckpt(self, step, filename):
+        """{'net', 'optim', 'step'} with ``optim`` in torch.optim's format over net.parameters(): main.py:94-100"""
+        optim = self.optim.torch_state_dict() if self._fused else _to_reference_layout(self.optim.state_dict(), self.bucket)
+        torch.save({'net': self.net.state_dict(), 'optim': optim, 'step': step}, filename)
+
+    def load_ckpt(self, filename, resume_schedule=False):
+        """main.py:102-107; returns the saved step.  Everything is copied INTO the tensors the trainer already holds, so a step that
+        is captured in a hipGraph goes on replaying.  The reference saves no scheduler state: after a load its StepLR restarts at
+        position 0 from the saved (already decayed) rate, and so does this one by default.  ``resume_schedule=True`` continues the
+        schedule instead: position ``ckpt['step']``, base rate the group's ``initial_lr`` (else the rate this trainer was built with)."""
+        if not self._fused and isinstance(self._g_fb, _HipStepGraph):
+            raise RuntimeError('FlowTrainer: torch.optim.load_state_dict re-binds the state tensors a captured hipGraph reads; load the '
+                               'checkpoint before the step is captured, or train with the fused optimizers (fused_adam=True)')
+        ckpt = torch.load(filename, map_location=next(self.net.parameters()).device)
+        self.net.load_state_dict(ckpt['net'])
+        step = ckpt['step']
+        group = ckpt['optim']['param_groups'][0]
+        lr = float(group['lr'])
+        base = float(group.get('initial_lr', self._base_lr)) if resume_schedule else lr
+        pos = int(step) if resume_schedule else 0
+        if self._fused:
+            self.optim.load_torch_state_dict(ckpt['optim'])
+            if self.decay_steps is not None:
+                self.optim.set_schedule(base, pos)
+        else:
+            lr_slot = self.optim.param_groups[0]['lr']          # (a device tensor when the framework optimizer is captured)
+            self.optim.load_state_dict(_from_reference_layout(ckpt['optim'], self.bucket))
+            g = self.optim.param_groups[0]
+            if self.decay_steps is not None:
+                lr = base * self.decay_ratio ** (pos // self.decay_steps)
+            if isinstance(lr_slot, torch.Tensor):
+                g['lr'] = lr_slot.fill_(lr)
+            else:
+                g['lr'] = lr
+            if self.decay_steps is not None:
+                g['initial_lr'] = base
+                self._sched = torch.optim.lr_scheduler.StepLR(self.optim, step_size=self.decay_steps, gamma=self.decay_ratio)
+                self._sched.last_epoch = pos
+                self._sched._last_lr = [lr]
+            else:
+                g.pop('initial_lr', None)
+        return step
 
     # -- evaluation -----------------------------------------------------------------------------------------------------
     @torch.no_grad()

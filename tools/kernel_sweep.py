@@ -222,7 +222,7 @@ def main():
     report('linear_bn_bwd 32x32 (all terms)', Nr * 32 * 4 * 6, lambda: F._launch_bwd([db], Nr, 32, 32))
     del x, out, res, gn, gst
 
-    # ---- NLL / Adam ---------------------------------------------------------------------------------------------------------------------
+    # ---- NLL / Adam / RMSprop ---------------------------------------------------------------------------------------------------------------------
     B = int(2 ** 24 * sc)
     z, ld, loss = torch.randn(B, 2, device=DEV), torch.zeros(B, device=DEV), torch.zeros((), device=DEV)
     report('nll_loss 2d', B * 12, lambda: N.call('nf_nll_loss', z.data_ptr(), ld.data_ptr(), loss.data_ptr(), B, 2, st()))
@@ -233,6 +233,35 @@ def main():
     report('adam_step (Glow-CIFAR: 8.38 M params)', n * 28,
            lambda: N.call('nf_adam_step', p.data_ptr(), gr.data_ptr(), m.data_ptr(), v.data_ptr(), stp.data_ptr(),
                           lr.data_ptr(), 0.9, 0.999, 1e-8, 0.0, 1.0, n, st()))
+    report('rmsprop_step (the same 8.38 M params)', n * 20,
+           lambda: N.call('nf_rmsprop_step', p.data_ptr(), gr.data_ptr(), v.data_ptr(), stp.data_ptr(), lr.data_ptr(), 0.99, 1e-8, 0.0,
+                          1.0, n, st()))
+    del p, gr, m, v
+
+    # ---- what the StepLR launch adds to a captured step: C2 (Glow 2-D, 32 steps, B = 4096) with and without a schedule ----------------------
+    for decay in (None, 50000):
+        name = 'c2 graph step, decay_steps=%s' % decay
+        if ONLY and not any(o in name for o in ONLY):
+            continue
+        us = c2_graph_step_us(decay)
+        print('%-46s %9.1f us per replay (median of 5 x 200)' % (name, us))
+
+
+def c2_graph_step_us(decay_steps):
+    from types import SimpleNamespace as NS
+    train = importlib.import_module('normalizing-flows-pytorch_amd.train')
+    data = importlib.import_module('normalizing-flows-pytorch_amd.data')
+    torch.manual_seed(0)
+    net = pkg.Glow((2, ), '2d', NS(layers=32, mixtures=None)).to(DEV)
+    tr = train.FlowTrainer(net, graph=True, warmup=2, decay_steps=decay_steps)
+    y = data.sample('moons', 4096, 1).to(DEV)
+    for _ in range(4):
+        tr.train_on_batch(y)
+    assert tr._g_fb is not None, 'the step was not captured'
+    times = []
+    for _ in range(5):
+        times.append(timeit(lambda: tr.train_on_batch(y), reps=200) * 1e6)
+    return sorted(times)[2]
 
 
 if __name__ == '__main__':
