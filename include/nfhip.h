@@ -1269,6 +1269,62 @@ int nf_cnf_noise(float* out, const int64_t* seed, int64_t E, int64_t B, int n_sa
  * adj_params OdeIntAdjoint.backward returns (odeint.py:282-284)                                                                       */
 int nf_cnf_fold(const double* slab, int64_t n_slabs, double* grads, int D, nf_stream_t stream);
 
+/* ---- Residual Flow, the whole stack [ActNorm, InvertibleResLinear] x L per launch (csrc/resflow.hip)  flows/resflow.py:9-38 -----------
+ * D <= 4 features, hidden width 32, two LipSwish layers, float32, contiguous (B, D).  At most NF_RESFLOW_MAX_LAYERS blocks per call; a
+ * longer stack is a sequence of calls (layer0 = index of the call's first block in the stack: it keys the in-kernel draws).
+ *
+ * table (DEVICE int64[L][16]): per block the device pointers  W_bar[3] | weight_u[3] | weight_v[3] | bias[3] | beta[2] | ActNorm log_scale |
+ *   ActNorm bias.  grads (DEVICE int64[L][10]): the gradient sinks  g_W_bar[3] | g_bias[3] | g_beta[2] | g_log_scale | g_bias(ActNorm).
+ * packed (L, n_tot), n_tot = nf_resflow_param_floats(D): the stack's EFFECTIVE parameters as the kernels stage them,
+ *   W1 (32 x D) | b1 | W2 (32 x 32) | b2 | W3 (D x 32) | b3 | beta1 beta2 | log_scale (D) | bias (D).
+ *
+ * Series estimator (mode 2): S <= 4 samples, lengths n and Hutchinson noise v from one of two sources.
+ *   explicit: n_terms int32 (L, 2, S) and noise float32 (L, 2, B, S, D).  Slot 0 is the Neumann surrogate's draw (sample 0 only; consumed
+ *     by nf_resflow_bwd), slot 1 the value estimator's (iresblock.py:127-137 draws them in this order).
+ *   in-kernel (noise == NULL): Philox4x32-10 + Box-Muller keyed by seed[0], stream offset seed[1] (device int64[2], the nf_cnf_*
+ *     convention), counter (row, layer, slot, sample).  The length is keyed WITHOUT the row -- one per block call for the whole batch, as
+ *     np.random.geometric in iresblock.py:66, :90 --: n = n_exact + ceil(log(u) / log(1 - p)), clamped to 64.
+ *   The coefficients are computed in the kernel from (n, n_exact, p): value (-1)^(k+1) / (k (1-p)^max(0, k-n_exact-1)) (iresblock.py:59-81),
+ *   Neumann (-1)^k / (1-p)^max(0, k-2) (iresblock.py:84-109).  fixed_n > 0: every value length is fixed_n (the `fixed` estimator,
+ *   iresblock.py:35-56, with n_exact >= fixed_n).                                                                                       */
+#define NF_RESFLOW_MAX_LAYERS 32
+#define NF_RESFLOW_INV_WG_MAX_ROWS 4096   /* the one-workgroup inverse serves B up to this (8 rows per thread of 512)                    */
+int nf_resflow_param_floats(int D, int* n_floats);
+/* flows/spectral_norm.py:26-43 for all 3 L matrices, one workgroup each (one power iteration, weight_u / weight_v updated in place), and
+ * the gather of every other parameter of the stack into `packed`                                                                        */
+int nf_resflow_spectral(const int64_t* table, float* packed, int L, int D, float coeff, float eps, nf_stream_t stream);
+/* ActNorm.forward (modules.py:244-250) + InvertibleResLinear.forward (iresblock.py:229-234) of every block, one row per thread.  y (B, D);
+ * ld (B) updated IN PLACE by `mode`: 0 untouched, 1 exact log-det (iresblock.py:17-32), 2 series.  save (L, B, D) or NULL: the block
+ * inputs (the ActNorm outputs) nf_resflow_bwd reads.                                                                                    */
+int nf_resflow_fwd(const float* x, float* y, float* ld, float* save, const float* packed, const int* n_terms, const float* noise,
+                   const int64_t* seed, int mode, int S, int n_exact, int fixed_n, float p, int L, int layer0, int64_t B, int D,
+                   nf_stream_t stream);
+int nf_resflow_bwd_slab_floats(int L, int64_t B, int D, int64_t* n_floats);
+/* The training backward of the stack in one launch, last block first (iresblock.py:84-109, :112-185 per block as nf_resmlp_train_bwd, the
+ * residual connection, and the ActNorm's autograd): g_y (B, D), g_ld (B; g_ld[0] scales the surrogate of the whole batch, iresblock.py:166;
+ * the log-det's own gradient passes through unchanged).  d_z (B, D): the running gradient, on return the gradient of the stack's input
+ * (may alias g_y).  The slot-0 draws come from the same source as the forward's.  Parameter gradients: per-workgroup totals in
+ * slab (nf_resflow_bwd_slab_floats), no atomics -- nf_resflow_spectral_bwd folds them in workgroup order, applies the autograd of the
+ * spectral normalisation (spectral_norm.py:36-43, u / v constant) and ADDS every total to its sink: bit-identical run to run.  Exactly one
+ * of grads / flat is given: flat (L, n_tot), laid out as `packed`, takes the place of the sinks (the caller hands views to autograd).  */
+int nf_resflow_bwd(const float* g_y, const float* g_ld, float* d_z, const float* save, const float* packed, const int* n_terms,
+                   const float* noise, const int64_t* seed, int S, float p, float* slab, int L, int layer0, int64_t B, int D,
+                   nf_stream_t stream);
+int nf_resflow_spectral_bwd(const int64_t* table, const int64_t* grads, float* flat, const float* slab, int L, int64_t B, int D, float coeff,
+                            float eps, nf_stream_t stream);
+/* ActNorm.backward + InvertibleResLinear.backward of every block, last first (iresblock.py:236-255, modules.py:252-256), in ONE workgroup
+ * for B <= NF_RESFLOW_INV_WG_MAX_ROWS: per block at most 100 iterations x <- z - g(x), each after one power iteration of the block's
+ * matrices (the reference runs one per g_fn call), left when no row of the batch moved by ftol or more (iresblock.py:248); then one more
+ * power iteration, the log-det estimate with sign -1 and the ActNorm inverse.  x (B, D), ld (B) in place, iters int32 (L): iterations per
+ * block.  Draws: n_terms (L, S), noise (L, B, S, D) (the value estimator's alone), or in-kernel (slot 1 keys).                          */
+int nf_resflow_inv(const float* z, float* x, float* ld, int* iters, const int64_t* table, float* packed, const int* n_terms,
+                   const float* noise, const int64_t* seed, int mode, int S, int n_exact, int fixed_n, float p, float coeff, float eps,
+                   float ftol, int L, int layer0, int64_t B, int D, nf_stream_t stream);
+/* the lengths and the noise the kernels draw for the seed words as they stand: slots = 2 the layout of nf_resflow_fwd / _bwd, slots = 1
+ * that of nf_resflow_inv (a test feeds them back as explicit arrays)                                                                    */
+int nf_resflow_draws(int* n_terms, float* noise, const int64_t* seed, int slots, int S, int n_exact, int fixed_n, float p, int L,
+                     int layer0, int64_t B, int D, nf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

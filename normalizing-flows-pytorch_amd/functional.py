@@ -8,6 +8,7 @@ own ``torch.no_grad`` inverse of the invertible 1x1 convolution (flows/modules.p
 modules.py:249,305,480); only the returned tensor is contractual.
 """
 import ctypes
+import os
 
 import torch
 
@@ -1132,6 +1133,205 @@ def planar_inverse(z, ld, layers, mids=False):
         if mids:
             return cur, ld, iters, mid
         return cur, ld, iters
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Residual Flow (flows/resflow.py, flows/iresblock.py): the whole stack [ActNorm, InvertibleResLinear] x L per launch (csrc/resflow.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+RESFLOW_STACK = os.environ.get('NF_RESFLOW_STACK', '1') != '0'     # 0: one ActNorm launch + the per-block kernels of csrc/resmlp.hip
+RESFLOW_MAX_LAYERS = 32       # include/nfhip.h NF_RESFLOW_MAX_LAYERS (checked against the header in tests/test_resflow_host.py)
+RESFLOW_P = 0.5               # the geometric law of the series lengths (iresblock.py:59, :84)
+_resflow_tables = {}          # (device index, pointers) -> device int64 table: uploaded once, so a captured step replays against it
+
+
+def _resflow_table(tensors, device):
+    key = (device.index, tuple(t.data_ptr() for t in tensors))
+    tab = _resflow_tables.get(key)
+    if tab is None:
+        if len(_resflow_tables) >= 64:
+            _resflow_tables.clear()
+        tab = torch.tensor(key[1], dtype=torch.int64).to(device)
+        _resflow_tables[key] = tab
+    return tab
+
+
+def resflow_param_floats(D):
+    """floats of one block's row of the packed parameter / gradient buffers: W1 | b1 | W2 | b2 | W3 | b3 | beta1 beta2 | log_scale | bias"""
+    return 32 * D + 32 + 1024 + 32 + D * 32 + D + 2 + 2 * D
+
+
+def _resflow_members(pairs):
+    """(table tensors in include/nfhip.h's order, parameters in the gradient table's order) of [(ActNorm, InvertibleResLinear), ..]"""
+    tab, params = [], []
+    for a, blk in pairs:
+        wbar, u, v, bias, beta = blk._stack_members()
+        tab += wbar + u + v + bias + beta + [a.log_scale, a.bias]
+        params += wbar + bias + beta + [a.log_scale, a.bias]
+    return tab, params
+
+
+def _resflow_series(blk, training):
+    """(mode, S, n_exact, fixed_n) of the estimator the reference picks (iresblock.py:131-137)"""
+    if training:
+        return 2, 1, 1, 0
+    if blk.estimator == 'exact':
+        return 1, 0, 0, 0
+    if blk.estimator == 'fixed':
+        return 2, 4, 8, 8
+    if blk.estimator == 'unbias':
+        return 2, 4, 8, 0
+    raise Exception('Unknown log-det estimator: %s' % (blk.estimator, ))
+
+
+def resflow_spectral_(pairs, D):
+    """spectral normalisation of every matrix of the stack in ONE launch (weight_u / weight_v updated in place): returns the packed
+    effective parameters (L, n_tot) and the device pointer table"""
+    tab, _ = _resflow_members(pairs)
+    dev = tab[0].device
+    table = _resflow_table([t.detach() for t in tab], dev)
+    packed = torch.empty((len(pairs), resflow_param_floats(D)), dtype=torch.float32, device=dev)
+    blk = pairs[0][1]
+    N.call('nf_resflow_spectral', N.ptr(table, (torch.int64, )), N.ptr(packed), len(pairs), D, float(blk.coeff), float(blk._sn_eps()), N.stream())
+    return packed, table
+
+
+def resflow_draws(seed, L, B, D, S, n_exact, fixed_n=0, slots=2, layer0=0):
+    """(n_terms int32 (L, slots, S), noise float32 (L, slots, B, S, D)) the kernels draw for the seed words ``seed`` (device int64[2]) as
+    they stand now; slots=1 is the inverse's layout (squeezed: (L, S), (L, B, S, D))"""
+    n_terms = torch.empty((L, slots, S), dtype=torch.int32, device=seed.device)
+    noise = torch.empty((L, slots, B, S, D), dtype=torch.float32, device=seed.device)
+    N.call('nf_resflow_draws', N.ptr(n_terms), N.ptr(noise), N.ptr(seed, (torch.int64, )), slots, S, n_exact, fixed_n, RESFLOW_P, L, layer0, B, D,
+           N.stream())
+    if slots == 1:
+        return n_terms[:, 0], noise[:, 0]
+    return n_terms, noise
+
+
+class _ResFlowStack(torch.autograd.Function):
+    """training forward of <= RESFLOW_MAX_LAYERS blocks (spectral launch + one stack launch) and its backward (one stack launch + the
+    fold / spectral-norm autograd launch, gradients added to the parameters' sinks where a GradBucket offers them)"""
+
+    @staticmethod
+    def forward(ctx, z, ld, cfg, n_terms, noise, seed, *params):
+        pairs, layer0 = cfg
+        B, D = z.shape
+        L = len(pairs)
+        packed, table = resflow_spectral_(pairs, D)
+        save = torch.empty((L, B, D), dtype=z.dtype, device=z.device)
+        out, ld_out = torch.empty_like(z), ld.clone()
+        N.call('nf_resflow_fwd', N.ptr(z), N.ptr(out), N.ptr(ld_out), N.ptr(save), N.ptr(packed), N.ptr(n_terms), N.ptr(noise),
+               N.ptr(seed, (torch.int64, )) if noise is None else None, 2, 1, 1, 0, RESFLOW_P, L, layer0, B, D, N.stream())
+        ctx.pairs, ctx.layer0, ctx.table = pairs, layer0, table
+        ctx.sinks = _sinks(*params)
+        ctx.save_for_backward(save, packed, n_terms, noise, seed, *params)
+        return out, ld_out
+
+    @staticmethod
+    def backward(ctx, g_y, g_ld):
+        save, packed, n_terms, noise, seed, *params = ctx.saved_tensors
+        L, B, D = save.shape
+        blk = ctx.pairs[0][1]
+        g_y, g_ld = _contig(g_y), _contig(g_ld)
+        n = ctypes.c_int64(0)
+        rc = N.load().nf_resflow_bwd_slab_floats(L, B, D, ctypes.byref(n))
+        if rc != 0:
+            raise N.NativeLibraryError('nf_resflow_bwd_slab_floats failed with code %d' % rc)
+        slab = torch.empty(max(int(n.value), 1), dtype=torch.float32, device=g_y.device)
+        d_z = torch.empty_like(g_y)
+        N.call('nf_resflow_bwd', N.ptr(g_y), N.ptr(g_ld), N.ptr(d_z), N.ptr(save), N.ptr(packed), N.ptr(n_terms), N.ptr(noise),
+               N.ptr(seed, (torch.int64, )) if noise is None else None, 1, RESFLOW_P, N.ptr(slab), L, ctx.layer0, B, D, N.stream())
+        if ctx.sinks is not None:
+            gtab, flat, ret = _resflow_table(ctx.sinks, g_y.device), None, [None] * len(params)
+        else:
+            nt = resflow_param_floats(D)
+            gtab, flat, ret = None, WS.zeros(L * nt, g_y.device).view(L, nt), []
+            o = (0, 32 * D + 32, 32 * D + 32 + 1024 + 32)                            # W1, W2, W3 in a row of flat
+            for l in range(L):
+                r = flat[l]
+                ret += [r[o[0]:o[0] + 32 * D].view(32, D), r[o[1]:o[1] + 1024].view(32, 32), r[o[2]:o[2] + 32 * D].view(D, 32),
+                        r[32 * D:32 * D + 32], r[o[1] + 1024:o[1] + 1056], r[o[2] + 32 * D:o[2] + 33 * D],
+                        r[o[2] + 33 * D:o[2] + 33 * D + 1], r[o[2] + 33 * D + 1:o[2] + 33 * D + 2],
+                        r[o[2] + 33 * D + 2:o[2] + 34 * D + 2].view(params[10 * l + 8].shape),
+                        r[o[2] + 34 * D + 2:o[2] + 35 * D + 2].view(params[10 * l + 9].shape)]
+        N.call('nf_resflow_spectral_bwd', N.ptr(ctx.table, (torch.int64, )), N.ptr(gtab, (torch.int64, )), N.ptr(flat), N.ptr(slab), L, B, D,
+               float(blk.coeff), float(blk._sn_eps()), N.stream())
+        return (d_z, g_ld, None, None, None, None) + tuple(ret)
+
+
+def resflow_flow(z, ld, pairs, draws='host', seed=None):
+    """[ActNorm, InvertibleResLinear] x L forward (flows/resflow.py:30-33) on initialised ActNorms: per <= RESFLOW_MAX_LAYERS blocks one
+    spectral-normalisation launch and one stack launch -- training (autograd on, blocks in training mode) through _ResFlowStack,
+    density evaluation (no_grad, eval mode) without a graph.  draws='host': lengths and noise from the host generators in the
+    reference's order (resflow.stack_draws); 'device': drawn in the kernels from ``seed`` (device int64[2]; seed[1] is advanced on the
+    device once per launch)."""
+    from . import resflow as RF
+    z = _contig(z)
+    blk = pairs[0][1]
+    training = blk.training
+    B, D = z.shape
+    mode, S, n_exact, fixed_n = _resflow_series(blk, training)
+    for i in range(0, len(pairs), RESFLOW_MAX_LAYERS):
+        run = pairs[i:i + RESFLOW_MAX_LAYERS]
+        n_terms = noise = None
+        if draws == 'host':
+            n_terms, noise = RF.stack_draws([b for _, b in run], z, training, 2)
+        elif seed is None:
+            raise RuntimeError("draws='device' needs the seed words (a device int64[2] tensor)")
+        sd = seed.clone() if (draws != 'host' and training) else seed            # the backward regenerates the slot-0 noise from these
+        if training:
+            _, params = _resflow_members(run)
+            z, ld = _ResFlowStack.apply(z, ld, (run, i), n_terms, noise, sd if draws != 'host' else None, *params)
+        else:
+            with torch.no_grad():
+                packed, _ = resflow_spectral_(run, D)
+                out, ld = torch.empty_like(z), ld.clone()
+                N.call('nf_resflow_fwd', N.ptr(z), N.ptr(out), N.ptr(ld), None, N.ptr(packed), N.ptr(n_terms), N.ptr(noise),
+                       N.ptr(sd, (torch.int64, )) if draws != 'host' else None, mode, S, n_exact, fixed_n, RESFLOW_P, len(run), i, B, D,
+                       N.stream())
+                z = out
+        if draws != 'host':
+            seed[1] += 1                                                            # a stream of its own for the next pass (device side)
+    return z, ld
+
+
+def resflow_inverse(z, ld, pairs, draws='host', seed=None):
+    """the inverse of the stack, last block first (iresblock.py:236-255, modules.py:252-256), for B <= NF_RESFLOW_INV_WG_MAX_ROWS: one
+    launch per <= RESFLOW_MAX_LAYERS blocks, no graph.  Returns (x, ld, iters) -- iters: int32 (L,), fixed-point iterations per block in
+    layer order (also left on every block as ``last_inverse_iters``)."""
+    from . import resflow as RF
+    with torch.no_grad():
+        z = _contig(z)
+        B, D = z.shape
+        L = len(pairs)
+        blk = pairs[0][1]
+        mode, S, n_exact, fixed_n = _resflow_series(blk, blk.training)
+        iters = torch.zeros(L, dtype=torch.int32, device=z.device)
+        ld = ld.clone()
+        out = torch.empty_like(z)
+        cur = z
+        for j in range(((L + RESFLOW_MAX_LAYERS - 1) // RESFLOW_MAX_LAYERS) - 1, -1, -1):
+            a, b = j * RESFLOW_MAX_LAYERS, min(L, (j + 1) * RESFLOW_MAX_LAYERS)
+            run = pairs[a:b]
+            n_terms = noise = None
+            if draws == 'host':
+                # the reference inverts the LAST block first: its draws come first in the host generators' streams
+                n_terms, noise = RF.stack_draws([blk_ for _, blk_ in run][::-1], z, blk.training, 1)
+                if n_terms is not None:
+                    n_terms, noise = n_terms.flip(0).contiguous(), noise.flip(0).contiguous()
+            elif seed is None:
+                raise RuntimeError("draws='device' needs the seed words (a device int64[2] tensor)")
+            tab, _ = _resflow_members(run)
+            table = _resflow_table([t.detach() for t in tab], z.device)
+            packed = torch.empty((len(run), resflow_param_floats(D)), dtype=torch.float32, device=z.device)
+            N.call('nf_resflow_inv', N.ptr(cur), N.ptr(out), N.ptr(ld), N.ptr(iters[a:b]), N.ptr(table, (torch.int64, )), N.ptr(packed),
+                   N.ptr(n_terms), N.ptr(noise), N.ptr(seed, (torch.int64, )) if draws != 'host' else None, mode, S, n_exact, fixed_n,
+                   RESFLOW_P, float(blk.coeff), float(blk._sn_eps()), float(blk.ftol), len(run), a, B, D, N.stream())
+            cur = out
+            if draws != 'host':
+                seed[1] += 1
+        for l, (_, blk_) in enumerate(pairs):
+            blk_.last_inverse_iters = iters[l]
+    return cur, ld, iters
 
 
 # ----------------------------------------------------------------------------------------------------------------------

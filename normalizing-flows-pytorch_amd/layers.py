@@ -42,6 +42,8 @@ class Compose(nn.Module):
     member carries forward hooks (the reference's debug mode registers NaN hooks, main.py:312-313)."""
 
     fuse = True
+    _resflow_draws = 'host'         # (ResFlow.draws: where the whole-stack ResFlow kernels take series lengths and noise from)
+    _resflow_seed = None            # (ResFlow.seed: device int64[2], the seed words of draws = 'device')
 
     def __init__(self, layers):
         super().__init__()
@@ -158,6 +160,33 @@ class Compose(nn.Module):
             j += step
         return run
 
+    def _resflow_run(self, i, z, step):
+        """the maximal run of [ActNorm (initialised), InvertibleResLinear] pairs from layer i on (step +1: i is the first pair's ActNorm;
+        -1: i is the last pair's block), as [(ActNorm, block), ..] in forward order -- blocks the HIP kernels serve (``_hip_ok``: D <= 4,
+        hidden width 32, two LipSwish layers, float32 on the GPU), of one mind (mode, estimator, coeff, ftol, noise source), no hooks.
+        While an ActNorm awaits its data-dependent initialisation the per-layer path runs."""
+        from .resflow import InvertibleResLinear
+        L, run = self.layers, []
+        if not (NF.RESFLOW_STACK and z.is_cuda):
+            return run
+        j = i if step > 0 else i - 1
+        while 0 <= j and j + 1 < len(L):
+            a, k = L[j], L[j + 1]
+            if not (type(a) is ActNorm and type(k) is InvertibleResLinear and a.initialized and k._hip_ok(z)):
+                break
+            if (a._forward_hooks or a._forward_pre_hooks or k._forward_hooks or k._forward_pre_hooks or a._backward_hooks or k._backward_hooks):
+                break
+            if step > 0 and not ((not k.training and not torch.is_grad_enabled()) or (k.training and torch.is_grad_enabled() and k.hip_training)):
+                break                                              # (the combinations the block itself serves with kernels, resflow.py)
+            if run:
+                f = run[0][1] if step > 0 else run[-1][1]
+                if (k.training, k.estimator, k.coeff, k.ftol, k.noise_on_cpu, k._sn_eps()) != \
+                        (f.training, f.estimator, f.coeff, f.ftol, f.noise_on_cpu, f._sn_eps()):
+                    break
+            run.append((a, k))
+            j += 2 * step
+        return run if step > 0 else run[::-1]
+
     def forward(self, z, log_df_dz):
         L, n, i = self.layers, len(self.layers), 0
         while i < n:
@@ -165,6 +194,11 @@ class Compose(nn.Module):
             if run:                                                # the run of planar layers: projection + one launch
                 z, log_df_dz = NF.planar_flow(z, log_df_dz, run)
                 i += len(run)
+                continue
+            run = self._resflow_run(i, z, 1) if self._fuse_now else []
+            if run:                                                # the run of residual blocks: a handful of launches whatever its length
+                z, log_df_dz = NF.resflow_flow(z, log_df_dz, run, self._resflow_draws, self._resflow_seed)
+                i += 2 * len(run)
                 continue
             run = self._realnvp_eval_run_at(i, z) if not torch.is_grad_enabled() else None
             if run is not None:                                    # density evaluation: the run in one launch, no exchange
@@ -323,6 +357,12 @@ class Compose(nn.Module):
             if run:                                                # the run of planar layers: one bisection launch (or 3 per layer)
                 z, log_df_dz, _ = NF.planar_inverse(z, log_df_dz, run[::-1])
                 i -= len(run)
+                continue
+            run = self._resflow_run(i, z, -1) if (self._fuse_now and z.dim() == 2
+                                                  and z.shape[0] <= N.header_constant('NF_RESFLOW_INV_WG_MAX_ROWS')) else []
+            if run:                                                # the run of residual blocks: the whole inverse in one workgroup
+                z, log_df_dz, _ = NF.resflow_inverse(z, log_df_dz, run, self._resflow_draws, self._resflow_seed)
+                i -= 2 * len(run)
                 continue
             run = self._glow_inverse_run_ending_at(i, z)
             if run is not None:

@@ -2,12 +2,15 @@
 Residual Flow (invertible residual blocks): flows/iresblock.py:17-301, flows/spectral_norm.py:5-72,
 flows/modules.py:215-222 (LipSwish), flows/resflow.py:9-38 -- SURVEY.md section 8(a) row a15.
 
-Everything runs on HIP kernels (csrc/resmlp.hip) for D <= 4: the evaluation-mode forward with all three log-det estimators
-on the per-sample exact Jacobian of the 2->32->32->2 LipSwish MLP, the fixed-point inverse (flag-gated iteration launches),
-spectral normalisation -- and the TRAINING step: the Russian-roulette value and the Neumann-series gradient estimator
-(iresblock.py:59-109, :112-185) with the network's second derivatives in closed form (nf_resmlp_train_bwd) instead of nested
-autograd sweeps; `hip_training = False` selects the PyTorch-autograd restatement (kept as the parity reference of the tests).
-No BASELINE config exercises this family.  Same module / parameter names as the reference, same estimator semantics
+Everything runs on HIP kernels for D <= 4: the evaluation-mode forward with all three log-det estimators on the per-sample
+exact Jacobian of the 2->32->32->2 LipSwish MLP, the fixed-point inverse, spectral normalisation -- and the TRAINING step: the
+Russian-roulette value and the Neumann-series gradient estimator (iresblock.py:59-109, :112-185) with the network's second
+derivatives in closed form instead of nested autograd sweeps; `hip_training = False` selects the PyTorch-autograd restatement
+(kept as the parity reference of the tests).  A run of [ActNorm, InvertibleResLinear] pairs inside a Compose takes the
+whole-stack kernels of csrc/resflow.hip (layers.Compose._resflow_run, functional.resflow_*): a handful of launches per pass
+whatever the depth; NF_RESFLOW_STACK=0, or a block on its own, takes the per-block kernels of csrc/resmlp.hip below.
+`ResFlow.draws = 'device'` moves the series lengths and the noise into the kernels (Philox), which is what lets
+train.FlowTrainer(graph=True) capture a ResFlow step.  Same module / parameter names as the reference, same estimator semantics
 (Russian-roulette series for training, `exact` / `fixed` / `unbias` for evaluation, fixed-point inverse with the
 batch-global exit), same RNG consumption order (np.random.geometric, then a normal draw) so seeded runs are
 comparable; `noise_on_cpu = True` draws the Hutchinson noise from the CPU generator (parity tests).
@@ -180,6 +183,22 @@ class InvertibleResLinear(nn.Module):
         return [self._weff[0], sn[0].module.bias, self._weff[1], sn[1].module.bias, self._weff[2], sn[2].module.bias,
                 acts[0].beta, acts[1].beta]
 
+    def _stack_members(self):
+        """([W_bar] * 3, [weight_u] * 3, [weight_v] * 3, [bias] * 3, [beta] * 2): what the whole-stack kernels read (functional.resflow_*)"""
+        mods = getattr(self, '_sn_mods', None)
+        if mods is None:
+            mods = ([m.module for m in self.g_fn if isinstance(m, SpectralNorm)], [m for m in self.g_fn if isinstance(m, LipSwish)])
+            object.__setattr__(self, '_sn_mods', mods)           # (a plain attribute: not a registered submodule list)
+        sn, acts = mods
+        for m in sn:
+            if 'weight' in m._parameters:                        # the reference deletes it on its first call
+                del m._parameters['weight']
+        return ([m._parameters['weight_bar'] for m in sn], [m._buffers['weight_u'] for m in sn], [m._buffers['weight_v'] for m in sn],
+                [m._parameters['bias'] for m in sn], [a._parameters['beta'] for a in acts])
+
+    def _sn_eps(self):
+        return next(m for m in self.g_fn if isinstance(m, SpectralNorm)).eps
+
     def _series(self, g_like, training):
         """(mode, noise, coef, n_terms, S): the estimator the reference would pick, noise drawn in its order."""
         if not training and self.estimator == 'exact':
@@ -251,6 +270,7 @@ class InvertibleResLinear(nn.Module):
                 N.call('nf_resmlp_fixed_point_step', N.ptr(z), N.ptr(x), *[N.ptr(t.detach()) for t in w], flags.data_ptr(),
                        it, float(self.ftol), B, D, N.stream())
             w = self._hip_weights()                      # the final g_fn(x) of the reference (one more power iteration)
+            self.last_inverse_iters = (1 + flags[:99].sum()).to(torch.int32)   # iteration it ran iff it == 0 or flags[it - 1]
             ld = log_df_dz.clone()
             self._hip_logdet(w, x, None, ld, -1.0, self.training)
             return x, ld
@@ -264,6 +284,80 @@ class InvertibleResLinear(nn.Module):
             x = x.detach().requires_grad_(True)
             logdet = self._estimate(self.g_fn(x), x)
         return x.detach(), log_df_dz - logdet.detach()
+
+
+def series_coefficients(n, n_exact, p=0.5, neumann=False):
+    """host restatement of the coefficients the whole-stack kernels compute from (n, n_exact, p) in float32 (csrc/resflow.hip
+    NfRfValueCoef / NfRfNeumannCoef): a running product pw = (1 - p)^max(0, k - n_exact - 1), then +-1 / (k pw) for the value
+    estimator (iresblock.py:59-81) and +-1 / pw for the Neumann surrogate (iresblock.py:84-109).  float32 array of n entries."""
+    q, pw = np.float32(1.0) - np.float32(p), np.float32(1.0)
+    out = np.zeros(n, dtype=np.float32)
+    for k in range(1, n + 1):
+        if k - n_exact - 1 > 0:
+            pw = np.float32(pw * q)
+        if neumann:
+            out[k - 1] = np.float32(-1.0 if k & 1 else 1.0) / pw
+        else:
+            out[k - 1] = np.float32(1.0 if k & 1 else -1.0) / np.float32(np.float32(k) * pw)
+    return out
+
+
+def series_length(u, n_exact, p=0.5):
+    """host restatement of the in-kernel length draw: n_exact + ceil(log(u) / log(1 - p)) for a uniform u in (0, 1), clamped to SERIES_MAXK"""
+    g = np.ceil(np.log(np.float32(u)) / np.log(np.float32(1.0) - np.float32(p)))
+    return int(min(n_exact + int(min(max(g, 1.0), SERIES_MAXK)), SERIES_MAXK))
+
+
+def stack_draws(blocks, x, training, slots):
+    """the series lengths and Hutchinson noise of ``blocks`` (in the order given) from the HOST generators, consumed exactly as the
+    per-block path consumes them -- per block np.random.geometric, then the normal draw, the Neumann surrogate's first (slots=2:
+    forward, iresblock.py:127-137; slots=1: the inverse, which has no surrogate) -- stacked into the explicit arrays of the whole-stack
+    kernels: n_terms int32 (L, slots, S), noise (L, slots, B, S, D); slots=1 squeezed.  (None, None) for the exact estimator (whose
+    forward still consumes the surrogate's draw)."""
+    B, D = x.shape
+    dev = x.device
+    L = len(blocks)
+    est = blocks[0].estimator
+    exact = not training and est == 'exact'
+    if training:
+        S, n_exact = 1, 1
+    elif est in ('fixed', 'unbias'):
+        S, n_exact = 4, 8
+    elif not exact:
+        raise Exception('Unknown log-det estimator: %s' % (est, ))
+    p = 0.5
+    nts = None if exact else np.zeros((L, slots, S), dtype=np.int32)
+    v0, v1 = [], []
+    for l, blk in enumerate(blocks):
+        if slots == 2:
+            n0 = min(int(1 + np.random.geometric(p)), SERIES_MAXK)
+            v = blk._randn_like(x)
+            if not exact:
+                nts[l, 0, 0] = n0
+                v0.append(v)
+        if exact:
+            continue
+        if not training and est == 'fixed':
+            v1.append(blk._randn_like(x, (B, S, D)))
+            nts[l, slots - 1, :] = 8
+        else:
+            vs = []
+            for s_ in range(S):
+                nts[l, slots - 1, s_] = min(int(n_exact + np.random.geometric(p)), SERIES_MAXK)
+                vs.append(blk._randn_like(x))
+            v1.append(vs[0].unsqueeze(1) if S == 1 else torch.stack(vs, dim=1))
+    if exact:
+        return None, None
+    val = torch.stack(v1, dim=0)                                                  # (L, B, S, D)
+    n_terms = torch.from_numpy(nts).to(dev)
+    if slots == 1:
+        return n_terms[:, 0].contiguous(), val.contiguous()
+    if training:                                                                  # S = 1: both slots are consumed
+        noise = torch.stack([torch.stack(v0, dim=0).unsqueeze(2), val], dim=1)
+    else:                                                                         # evaluation draws the surrogate's noise and discards it
+        noise = torch.zeros((L, 2, B, S, D), dtype=x.dtype, device=dev)
+        noise[:, 1] = val
+    return n_terms, noise.contiguous()
 
 
 class _ResidualBranch(torch.autograd.Function):
@@ -380,12 +474,28 @@ class ResFlow(nn.Module):
             layers.append(InvertibleResLinear(self.dims[0], self.dims[0], coeff=cfg.spnorm_coeff,
                                               logdet_estimator=cfg.logdet))
         self.net = Compose(layers)
+        # seed words of the in-kernel draws (draws = 'device'): seed, stream offset; not in the state_dict
+        self.register_buffer('seed', torch.zeros(2, dtype=torch.int64), persistent=False)
+
+    @property
+    def draws(self):
+        """'host' (default): series lengths and noise from np.random / torch generators in the reference's order; 'device': drawn in the
+        whole-stack kernels from ``seed`` (what a captured training step needs: a replay draws afresh)"""
+        return self.net._resflow_draws
+
+    @draws.setter
+    def draws(self, value):
+        if value not in ('host', 'device'):
+            raise ValueError("draws is 'host' or 'device', got %r" % (value, ))
+        self.net._resflow_draws = value
 
     def _zero_ld(self, z):
         return torch.zeros(z.size(0), dtype=z.dtype, device=z.device)
 
     def forward(self, z):
+        self.net._resflow_seed = self.seed
         return self.net(z, self._zero_ld(z))
 
     def backward(self, z):
+        self.net._resflow_seed = self.seed
         return self.net.backward(z, self._zero_ld(z))

@@ -306,6 +306,14 @@ class FlowTrainer:
             graph = False
         self.sampler = sampler      # data.DeviceSampler: train_on_batch() without a batch draws one on the device, inside the graph
         on_gpu = next(net.parameters()).is_cuda
+        if graph and on_gpu:
+            # a Residual Flow draws its series lengths and noise from the host generators by default: a captured step would replay one
+            # frozen draw (or fail at capture on the host-to-device copies).  Its whole-stack kernels draw on the device instead.
+            from . import functional as NF
+            from .resflow import ResFlow
+            for m_ in net.modules():
+                if isinstance(m_, ResFlow) and NF.RESFLOW_STACK:
+                    m_.draws = 'device'
         fused_adam = bool(fused_adam) and on_gpu
         self.bucket = nfdist.GradBucket(net.parameters(), process_group, flatten_params=fused_adam)
         self.graph = bool(graph)
