@@ -281,9 +281,8 @@ def call(name, *args):
 
 def persistent_timeouts():
     """spin loops of the persistent kernels that gave up since load / the last reset (must be 0); synchronises the device."""
-    import ctypes as _c
-    v = _c.c_int(0)
-    rc = load().nf_persistent_timeouts(_c.byref(v))
+    v = ctypes.c_int(0)
+    rc = load().nf_persistent_timeouts(ctypes.byref(v))
     if rc != 0:
         raise NativeLibraryError('nf_persistent_timeouts failed with code %d' % rc)
     return int(v.value)

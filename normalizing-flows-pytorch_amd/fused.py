@@ -10,6 +10,7 @@ Fused conditioner networks on the fp32-MFMA linear + BatchNorm kernels (csrc/lin
 Both are exact restatements of the module math in training mode (batch statistics, gradients through the
 statistics, running-statistics bookkeeping) and in evaluation mode (running statistics).
 """
+import collections
 import ctypes
 import os as _os
 
@@ -17,6 +18,7 @@ import torch
 
 from . import _native as N
 from . import workspace as WS
+from .functional import PluHolder, _owned_ld, _sinks, flush_head_params, grad_sink
 
 BN_EPS, BN_MOMENTUM, WN_EPS = 1.0e-5, 0.1, 1.0e-5
 H = 32  # hidden width of every reference conditioner (base_filters=32)
@@ -139,7 +141,6 @@ class _FusedMLP(torch.autograd.Function):
                            bias=lin[nl - 1][2], out=out, **bn_kw(nb - 1))], Nrows, H, O_out, training)
         ctx.save_for_backward(x, ws, *acts, *[t for l in lin for t in l[:2]], *[t for b in bns for t in b[:2]])
         ctx.meta = (n_blocks, Nrows, I0, O_out, bool(training))
-        from .functional import _sinks
         ctx.sinks = _sinks(*[t for l in lin for t in l], *[t for b in bns for t in b[:2]])
         return out
 
@@ -241,24 +242,157 @@ def _ptr_table(tensors):
     return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# Tensor-list layouts of the whole-step kernels.  Every list is a C-ABI contract (include/nfhip.h): the pointer tables are read by
+# position, and so are the gradient tables, which hold one slot per LEARNABLE tensor in the order of ``learn``.
+# ----------------------------------------------------------------------------------------------------------------------
+_Layout = collections.namedtuple('_Layout', 'n head learn ghead gnet')
+# n: tensors in the list, the first ``head`` of them the step's own, the rest its conditioner nets'; learn: indices of the
+# gradient-bearing ones in gradient-table order; ghead / gnet: the slices of that order which hold the step's own gradients
+# and the nets' gradient table
+
+
+def _mlp_learn(nl, nb):
+    """(v, g, bias) of the nl linears, then (gamma, beta) of each of the nb BatchNorms of _mlp_tensors' 3 nl + 5 nb tensors"""
+    return tuple(range(3 * nl)) + tuple(3 * nl + 5 * j + k for j in range(nb) for k in (0, 1))
+
+
+_MLP_LEARN = _mlp_learn(6, 5)          # the two-block conditioner the persistent kernels take (mlp_chain_usable)
+# one MADE net of _made_tensors: (weight, bias) of the 4 masked linears, then (gamma, beta) of the 3 BatchNorms
+_MADE_LEARN = tuple(3 * l + k for l in range(4) for k in (0, 2)) + tuple(12 + 5 * j + k for j in range(3) for k in (0, 1))
+
+
+def _step_layout(head, head_learn, nets, head_grads_last=False):
+    """nets: [(tensors, learn indices)] of the conditioner nets that follow the ``head`` head tensors"""
+    learn, at = [], head
+    for n, net_learn in nets:
+        learn += [at + i for i in net_learn]
+        at += n
+    if head_grads_last:
+        return _Layout(at, head, tuple(learn) + tuple(head_learn), slice(len(learn), None), slice(0, len(learn)))
+    return _Layout(at, head, tuple(head_learn) + tuple(learn), slice(0, len(head_learn)), slice(len(head_learn), None))
+
+
+_MLP = _step_layout(0, (), [(43, _MLP_LEARN)])                               # _mlp_tensors
+_MADE = _step_layout(0, (), [(27, _MADE_LEARN)])                               # _made_tensors
+_GLOW = _step_layout(11, (0, 1, 3, 4, 8, 9, 10), [(43, _MLP_LEARN)])         # _glow_head + _mlp_tensors
+_REALNVP = _step_layout(8, (6, 7), [(43, _MLP_LEARN)])                       # _realnvp_head + _mlp_tensors
+_MAF = _step_layout(9, (7, 8), [(27, _MADE_LEARN)] * 2, head_grads_last=True)  # _maf_head + _made_tensors of net s, of net t
+
+
+def _learnables(layout, tensors):
+    """the gradient-bearing tensors of a list, in the order the C ABI's gradient tables expect"""
+    return [tensors[i] for i in layout.learn]
+
+
+def _place_grads(layout, grads):
+    """the inverse: gradients in gradient-table order -> one autograd slot per tensor of the list, None at the buffers"""
+    out = [None] * layout.n
+    for i, g in zip(layout.learn, grads):
+        out[i] = g
+    return tuple(out)
+
+
+def _glow_head(actnorm, conv, coupling, P=None):
+    return [actnorm.log_scale, actnorm.bias, conv.P if P is None else P, conv.L, conv.U, conv.L_mask, conv.U_mask, conv.sign_s,
+            conv.log_s, coupling.s_log_scale, coupling.s_bias]
+
+
+def _glow_inverse_head(actnorm, conv, coupling):
+    """the Glow head with the pivots' row-swap matrix in the P slot (nf_glow_step_vec_inv)"""
+    return _glow_head(actnorm, conv, coupling, conv._pivot_matrix().contiguous())
+
+
+def _realnvp_head(bn, coupling):
+    return [bn.log_gamma, bn.beta, bn.batch_mean, bn.batch_var, bn.running_mean, bn.running_var, coupling.s_log_scale,
+            coupling.s_bias]
+
+
+def _maf_head(bn, ar):
+    return [bn.log_gamma, bn.beta, bn.batch_mean, bn.batch_var, bn.running_mean, bn.running_var, ar.perm, ar.s_log_scale, ar.s_bias]
+
+
+def _made_tensors(net, masks=None):
+    """masks: the net's drawn masks (None: placeholders, for callers that only ask which tensors learn -- a draw moves the RNG)"""
+    ts = []
+    for l in range(net.num_hidden + 1):
+        ts += [net.weights[l], None if masks is None else masks[l], net.biases[l]]
+    for bn in net.bnorms:
+        ts += [bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked]
+    return ts
+
+
+def _glow_step_tensors(actnorm, conv, coupling):
+    return _glow_head(actnorm, conv, coupling) + _mlp_tensors(coupling.net)
+
+
+def _realnvp_step_tensors(bn, coupling):
+    return _realnvp_head(bn, coupling) + _mlp_tensors(coupling.net)
+
+
+def _maf_step_tensors(bn, ar, masks_s=None, masks_t=None):
+    return _maf_head(bn, ar) + _made_tensors(ar.net_s, masks_s) + _made_tensors(ar.net_t, masks_t)
+
+
+def _detached(tensors):
+    return [t.detach() for t in tensors]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Per-device scratch of the backward kernels, kept for the life of the process
+# ----------------------------------------------------------------------------------------------------------------------
+_SCRATCH = {}              # (header constant, times, device) -> buffer; (name, device) -> (slabs, rec); ('retired', device) -> [pairs]
+_GRAPH_SEEN = [False]      # a hipGraph capture has asked for the deferred-fold scratch at least once (only then can a graph hold its address)
+
+
+def _device_scratch(const, device, times=1):
+    """``times`` x the header constant ``const`` floats; launches on a stream are ordered, so one buffer per device serves
+    every call."""
+    key = (const, times, device)
+    t = _SCRATCH.get(key)
+    if t is None:
+        t = _SCRATCH[key] = torch.empty(times * N.header_constant(const), dtype=torch.float32, device=device)
+    return t
+
+
+def _scratch_pair(name, n_slabs, n_rec, device):
+    """(slabs_all, head_rec) of a deferred fold, kept across calls and replaced by a larger pair when outgrown."""
+    key = (name, device)
+    t = _SCRATCH.get(key)
+    if _capturing():
+        _GRAPH_SEEN[0] = True
+    if t is None or t[0].numel() < n_slabs or t[1].numel() < n_rec:
+        if t is not None and _GRAPH_SEEN[0]:
+            # an outgrown pair may be in the kernel arguments of a captured hipGraph (the whole-flow backward with its deferred fold):
+            # it is retired, not freed -- a later replay must not scribble over whatever the allocator placed there.  (While nothing
+            # captured can hold its address yet, the outgrown pair is simply freed.)
+            _SCRATCH.setdefault(('retired', device), []).append(t)
+        t = _SCRATCH[key] = (torch.empty(n_slabs, dtype=torch.float32, device=device),
+                             torch.empty(n_rec, dtype=torch.float32, device=device))
+    return t
+
+
 def mlp_chain_usable(mlp, x):
     return (len(mlp.mid_block) == 2 and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32
             and 0 < x.shape[0] <= N.mlp_max_rows())
 
 
-def mlp_chain_forward_nograd(mlp, x, training):
-    """forward only (no autograd graph); returns (out, save_stats)."""
-    ts = _mlp_tensors(mlp)
-    x = x.contiguous()
+def _mlp_chain_fwd(x, tensors, training):
+    """the launch of nf_mlp_chain_fwd on contiguous x; returns (out, save_stats)"""
     Nrows, I0 = x.shape
-    O_out = ts[15].shape[0]
+    O_out = tensors[15].shape[0]
     out = torch.empty(Nrows, O_out, dtype=torch.float32, device=x.device)
     save = torch.empty(5, 2, H, dtype=torch.float32, device=x.device)
     ws = WS.zeros(N.header_constant('NF_MLP_WS_FLOATS'), x.device)
-    tab = _ptr_table([t.detach() for t in ts])
+    tab = _ptr_table(tensors)
     N.call('nf_mlp_chain_fwd', N.ptr(x), ctypes.addressof(tab), N.ptr(out), N.ptr(save), N.ptr(ws), Nrows, I0, O_out,
            int(training), BN_EPS, BN_MOMENTUM, WN_EPS, N.stream())
     return out, save
+
+
+def mlp_chain_forward_nograd(mlp, x, training):
+    """forward only (no autograd graph); returns (out, save_stats)."""
+    return _mlp_chain_fwd(x.contiguous(), _detached(_mlp_tensors(mlp)), training)
 
 
 def mlp_forward(mlp, x, chain=None):
@@ -272,16 +406,9 @@ def mlp_forward(mlp, x, chain=None):
     return _FusedMLP.apply(x, mlp.training, len(mlp.mid_block), *tensors)
 
 
-_MLP_SLABS = {}
-
-
 def _mlp_slabs(device):
-    """scratch of nf_mlp_chain_bwd (per-workgroup weight-gradient partials); launches on a stream are ordered, so one
-    buffer per device serves every layer."""
-    t = _MLP_SLABS.get(device)
-    if t is None:
-        t = _MLP_SLABS[device] = torch.empty(N.header_constant('NF_MLP_BWD_SLAB_FLOATS'), dtype=torch.float32, device=device)
-    return t
+    """scratch of nf_mlp_chain_bwd (per-workgroup weight-gradient partials), one buffer for every layer"""
+    return _device_scratch('NF_MLP_BWD_SLAB_FLOATS', device)
 
 
 class _FusedMLPChain(torch.autograd.Function):
@@ -289,34 +416,21 @@ class _FusedMLPChain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, training, *tensors):
-        nl, nb = 6, 5
         x = x.contiguous()
-        Nrows, I0 = x.shape
-        O_out = tensors[15].shape[0]
-        dev = x.device
-        out = torch.empty(Nrows, O_out, dtype=torch.float32, device=dev)
-        save = torch.empty(nb, 2, H, dtype=torch.float32, device=dev)
-        ws = WS.zeros(N.header_constant('NF_MLP_WS_FLOATS'), dev)
-        tab = _ptr_table(tensors)
-        N.call('nf_mlp_chain_fwd', N.ptr(x), ctypes.addressof(tab), N.ptr(out), N.ptr(save), N.ptr(ws), Nrows, I0, O_out,
-               int(training), BN_EPS, BN_MOMENTUM, WN_EPS, N.stream())
+        out, save = _mlp_chain_fwd(x, tensors, training)
         ctx.save_for_backward(x, save, *tensors)
-        ctx.meta = (Nrows, I0, O_out, bool(training))
-        from .functional import _sinks
-        learn = list(tensors[:3 * nl]) + [t for j in range(nb) for t in tensors[3 * nl + 5 * j:3 * nl + 5 * j + 2]]
-        ctx.sinks = _sinks(*learn)
+        ctx.meta = (x.shape[0], x.shape[1], out.shape[1], bool(training))
+        ctx.sinks = _sinks(*_learnables(_MLP, tensors))
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        nl, nb = 6, 5
         Nrows, I0, O_out, training = ctx.meta
         x, save, *tensors = ctx.saved_tensors
         dev = x.device
         g_out = g_out.contiguous()
-        learn = list(tensors[:3 * nl]) + [t for j in range(nb) for t in tensors[3 * nl + 5 * j:3 * nl + 5 * j + 2]]
         direct = ctx.sinks is not None
-        dst = ctx.sinks if direct else [torch.empty_like(t) for t in learn]
+        dst = ctx.sinks if direct else [torch.empty_like(t) for t in _learnables(_MLP, tensors)]
         g_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         ws = WS.zeros(N.header_constant('NF_MLP_WS_FLOATS'), dev)
         tab, gtab = _ptr_table(tensors), _ptr_table(dst)
@@ -324,10 +438,7 @@ class _FusedMLPChain(torch.autograd.Function):
                int(direct), N.ptr(ws), N.ptr(_mlp_slabs(dev)), Nrows, I0, O_out, int(training), BN_EPS, WN_EPS, N.stream())
         if direct:
             return (g_x, None) + (None, ) * len(tensors)
-        grads = list(dst[:3 * nl])
-        for j in range(nb):
-            grads += [dst[3 * nl + 2 * j], dst[3 * nl + 2 * j + 1], None, None, None]
-        return (g_x, None) + tuple(grads)
+        return (g_x, None) + _place_grads(_MLP, dst)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -374,7 +485,6 @@ class _FusedMADEPair(torch.autograd.Function):
             keep += [BN(n, j)[0] for j in range(nh)] + [BN(n, j)[1] for j in range(nh)]
         ctx.save_for_backward(*keep)
         ctx.meta = (nh, Nrows, D, bool(training))
-        from .functional import _sinks
         sink_in = []
         for n in range(2):
             sink_in += [W(n, l) for l in range(nh + 1)] + [Bs(n, l) for l in range(nh + 1)]
@@ -494,16 +604,10 @@ def _flowpp_fwd_args(ts, F_):
             c1b.data_ptr() + 4 * 2 * F_, N.ptr(c2w), N.ptr(c2b), N.ptr(l2g), N.ptr(l2b), N.ptr(W5), N.ptr(b5)]
 
 
-_FPP_WS = {}
-
-
 def flowpp_bwd_workspace(device):
     """the partial-sum slabs of nf_flowpp_cond_bwd; one per device: backward launches on a stream are ordered, the next
     call may overwrite what the previous call's second kernel has already folded."""
-    ws = _FPP_WS.get(device)
-    if ws is None:
-        ws = _FPP_WS[device] = torch.empty(N.header_constant('NF_FLOWPP_BWD_WS_FLOATS'), dtype=torch.float32, device=device)
-    return ws
+    return _device_scratch('NF_FLOWPP_BWD_WS_FLOATS', device)
 
 
 class FlowppFinDesc(ctypes.Structure):
@@ -578,7 +682,6 @@ class _FusedFlowppCond(torch.autograd.Function):
         Nrows, I0 = x.shape
         O = ts[13].shape[0]
         g_out = g_out.contiguous()
-        from .functional import _sinks
         sinks = _sinks(*ts)
         if sinks is not None:
             dst, direct = sinks, True
@@ -634,7 +737,7 @@ class _GlowStepVec(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, ld, odd, training, *tensors):
-        head, mlp = tensors[:11], tensors[11:]
+        head, mlp = tensors[:_GLOW.head], tensors[_GLOW.head:]
         z = z.contiguous()
         Nrows, D = z.shape
         y = torch.empty_like(z)
@@ -645,50 +748,36 @@ class _GlowStepVec(torch.autograd.Function):
                N.ptr(save), N.ptr(ws), Nrows, D, int(odd), int(training), BN_EPS, BN_MOMENTUM, WN_EPS, N.stream())
         ctx.save_for_backward(z, save, *tensors)
         ctx.meta = (int(odd), bool(training))
-        from .functional import _sinks
-        nl, nb = 6, 5
-        learn_h = [head[0], head[1], head[3], head[4], head[8], head[9], head[10]]
-        learn_m = list(mlp[:3 * nl]) + [t for j in range(nb) for t in mlp[3 * nl + 5 * j:3 * nl + 5 * j + 2]]
-        ctx.sinks = _sinks(*(learn_h + learn_m))
+        ctx.sinks = _sinks(*_learnables(_GLOW, tensors))
         ctx.mark_dirty(ld)
         return y, ld
 
     @staticmethod
     def backward(ctx, g_y, g_ld):
-        nl, nb = 6, 5
         odd, training = ctx.meta
         z, save, *tensors = ctx.saved_tensors
-        head, mlp = tensors[:11], tensors[11:]
+        head, mlp = tensors[:_GLOW.head], tensors[_GLOW.head:]
         Nrows, D = z.shape
         dev = z.device
         g_y = g_y.contiguous()
         g_ld = None if g_ld is None else g_ld.contiguous()
-        learn_h = [head[0], head[1], head[3], head[4], head[8], head[9], head[10]]
-        learn_m = list(mlp[:3 * nl]) + [t for j in range(nb) for t in mlp[3 * nl + 5 * j:3 * nl + 5 * j + 2]]
         direct = ctx.sinks is not None
-        dst = ctx.sinks if direct else [torch.empty_like(t) for t in learn_h + learn_m]
+        dst = ctx.sinks if direct else [torch.empty_like(t) for t in _learnables(_GLOW, tensors)]
         g_z = torch.empty_like(z)
         ws = WS.zeros(N.header_constant('NF_MLP_WS_FLOATS'), dev)
         htab, mtab = _ptr_table(head), _ptr_table(mlp)
-        hg, mg = _ptr_table(dst[:7]), _ptr_table(dst[7:])
+        hg, mg = _ptr_table(dst[_GLOW.ghead]), _ptr_table(dst[_GLOW.gnet])
         N.call('nf_glow_step_vec_bwd', N.ptr(z), N.ptr(g_y), _p(g_ld), N.ptr(g_z), ctypes.addressof(htab), ctypes.addressof(mtab),
                N.ptr(save), ctypes.addressof(hg), ctypes.addressof(mg), int(direct), N.ptr(ws), N.ptr(_mlp_slabs(dev)), Nrows, D,
                odd, int(training), BN_EPS, WN_EPS, N.stream())
         if direct:
             return (g_z, g_ld, None, None) + (None, ) * len(tensors)
-        gh = [dst[0], dst[1], None, dst[2], dst[3], None, None, None, dst[4], dst[5], dst[6]]
-        gm = list(dst[7:7 + 3 * nl])
-        for j in range(nb):
-            gm += [dst[7 + 3 * nl + 2 * j], dst[7 + 3 * nl + 2 * j + 1], None, None, None]
-        return (g_z, g_ld, None, None) + tuple(gh) + tuple(gm)
+        return (g_z, g_ld, None, None) + _place_grads(_GLOW, dst)
 
 
 def glow_step_vec(z, ld, actnorm, conv, coupling):
     """ActNorm ``actnorm`` -> InvertibleConv1x1 ``conv`` -> AffineCoupling ``coupling`` on (N, D) data, fused."""
-    from .functional import _owned_ld
-    head = [actnorm.log_scale, actnorm.bias, conv.P, conv.L, conv.U, conv.L_mask, conv.U_mask, conv.sign_s, conv.log_s,
-            coupling.s_log_scale, coupling.s_bias]
-    return _GlowStepVec.apply(z, _owned_ld(ld), int(coupling.odd), coupling.net.training, *(head + _mlp_tensors(coupling.net)))
+    return _GlowStepVec.apply(z, _owned_ld(ld), int(coupling.odd), coupling.net.training, *_glow_step_tensors(actnorm, conv, coupling))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -723,7 +812,6 @@ def _capturing():
 
 class _FlowTableCache:
     def __init__(self, limit):
-        import collections
         self.limit = int(limit)
         self.entries = collections.OrderedDict()      # key -> [table, pinned]
         self.host = {}                                # device table pointer -> host copy of the same records
@@ -754,154 +842,156 @@ class _FlowTableCache:
 
 _GLOW_FLOW_TABLES = _FlowTableCache(32)
 _GLOW_FLOW_HOST = _GLOW_FLOW_TABLES.host          # device table pointer -> the host copy of the same records
-_GLOW_FLOW_SLABS = {}
-_GRAPH_SEEN = [False]      # a hipGraph capture has asked for the deferred-fold scratch at least once (only then can a graph hold its address)
+
+
+def _row_blocks(Nrows):
+    rpb = N.header_constant('NF_MLP_ROWS_PER_BLOCK')
+    return (Nrows + rpb - 1) // rpb
 
 
 def _glow_steps_scratch(S, blocks, device):
-    """(slabs_all, head_rec) of the deferred fold: a slab region per step and workgroup, kept across calls."""
-    key = ('steps', device)
-    n = S * blocks * N.header_constant('NF_MLP_BWD_SLAB_WG_FLOATS')
-    t = _GLOW_FLOW_SLABS.get(key)
-    if torch.cuda.is_current_stream_capturing():
-        _GRAPH_SEEN[0] = True
-    if t is None or t[0].numel() < n or t[1].numel() < S * blocks * 64:
-        if t is not None and torch.cuda.is_current_stream_capturing() is False and not _GRAPH_SEEN[0]:
-            pass                                   # nothing captured yet can hold its address: the outgrown pair is simply freed
-        elif t is not None:
-            # an outgrown pair may be in the kernel arguments of a captured hipGraph (the whole-flow backward with its deferred fold):
-            # it is retired, not freed -- a later replay must not scribble over whatever the allocator placed there
-            _GLOW_FLOW_SLABS.setdefault(('retired', device), []).append(t)
-        t = _GLOW_FLOW_SLABS[key] = (torch.empty(n, dtype=torch.float32, device=device),
-                                     torch.empty(S * blocks * 64, dtype=torch.float32, device=device))
-    return t
+    """(slabs_all, head_rec) of the deferred fold: a slab region per step and workgroup."""
+    return _scratch_pair('steps', S * blocks * N.header_constant('NF_MLP_BWD_SLAB_WG_FLOATS'), S * blocks * 64, device)
 
 
 def _glow_flow_slabs(device):
-    t = _GLOW_FLOW_SLABS.get(device)
-    if t is None:
-        t = _GLOW_FLOW_SLABS[device] = torch.empty(2 * N.header_constant('NF_MLP_BWD_SLAB_FLOATS'), dtype=torch.float32,
-                                                   device=device)
-    return t
+    return _device_scratch('NF_MLP_BWD_SLAB_FLOATS', device, 2)
 
 
-def _glow_step_learnables(head, mlp):
-    nl, nb = 6, 5
-    learn_h = [head[0], head[1], head[3], head[4], head[8], head[9], head[10]]
-    learn_m = list(mlp[:3 * nl]) + [t for j in range(nb) for t in mlp[3 * nl + 5 * j:3 * nl + 5 * j + 2]]
-    return learn_h + learn_m
+def _glow_pack(rec, htab, mtab, gh, mg, D, odd):
+    hg = None if gh is None else _ptr_table(gh)
+    N.call('nf_glow_flow_pack', rec, htab, mtab, None if hg is None else ctypes.addressof(hg), mg, D, odd)
 
 
-def _glow_flow_table(steps, sinks, D, device):
-    """device array of the steps' pointer records (nf_glow_flow_pack), cached while every pointer stays where it is.
-    steps: [(odd, head tensors, mlp tensors)]; sinks: per step the 35 gradient buffers (or None: forward only)."""
-    key = (device, D, tuple(int(odd) for odd, _, _ in steps),
-           tuple(t.data_ptr() for _, h, m in steps for t in list(h) + list(m)),
+def _realnvp_pack(rec, htab, mtab, gh, mg, D, odd, eps, momentum):
+    """momentum: of the flow BatchNorm in training mode, else FBN_RUNNING | FBN_BATCH_BUFFERS (it reads constants)"""
+    g_scale, g_bias = (None, None) if gh is None else gh
+    N.call('nf_realnvp_flow_pack', rec, htab, mtab, N.ptr(g_scale), N.ptr(g_bias), mg, D, odd, eps, momentum)
+
+
+# What tells a run of RealNVP steps from a run of Glow steps.  prefix: of the C-ABI entry points; tensors / meta: a step's modules ->
+# its tensor list (``layout``) / the scalars that end its pack call; training_arg: the launches take the conditioners' mode;
+# save_floats(N, D): per step; regions(N, D): weight-gradient partials per step that the whole-flow backward leaves to the deferred fold
+_FlowFamily = collections.namedtuple('_FlowFamily', 'prefix layout tensors meta pack training_arg save_floats regions')
+_GLOW_RUN = _FlowFamily('nf_glow', _GLOW, _glow_step_tensors, lambda a, c, k: (int(k.odd), ), _glow_pack, True,
+                        lambda Nrows, D: N.header_constant('NF_GLOW_FLOW_SAVE_FLOATS'), lambda Nrows, D: _row_blocks(Nrows))
+# (save: S statistics records, then -- for the shapes the one-workgroup kernels take -- the stash of BatchNorm inputs: the library says
+# how much; that kernel also leaves its own number of partials)
+_REALNVP_RUN = _FlowFamily('nf_realnvp', _REALNVP, _realnvp_step_tensors,
+                           lambda bn, k: (int(k.odd), float(bn.eps), float(bn.momentum)), _realnvp_pack, False,
+                           lambda Nrows, D: int(N.load().nf_realnvp_flow_save_floats(Nrows, D)),
+                           lambda Nrows, D: int(N.load().nf_realnvp_flow_bwd_regions(Nrows, D)))
+
+
+def _flow_table(fam, metas, steps, sinks, D, device):
+    """device array of the steps' pointer records (fam.pack), cached while every pointer stays where it is.
+    steps: per step its fam.layout.n tensors; metas: per step fam.meta's tuple; sinks: per step the gradient buffers of its
+    learnables (or None: forward only)."""
+    key = (fam.prefix, device, D, metas, tuple(t.data_ptr() for ts in steps for t in ts),
            None if sinks is None else tuple(t.data_ptr() for g in sinks for t in g))
     hit = _GLOW_FLOW_TABLES.get(key)
     if hit is not None:
         return hit
-    lib = N.load()
-    nbytes = int(lib.nf_glow_flow_step_bytes())
+    L = fam.layout
+    nbytes = int(N.load().nf_glow_flow_step_bytes())
     host = (ctypes.c_ubyte * (nbytes * len(steps)))()
-    for i, (odd, head, mlp) in enumerate(steps):
-        htab, mtab = _ptr_table(head), _ptr_table(mlp)
-        if sinks is None:
-            hg = mg = None
-        else:
-            hgt, mgt = _ptr_table(sinks[i][:7]), _ptr_table(sinks[i][7:])
-            hg, mg = ctypes.addressof(hgt), ctypes.addressof(mgt)
-        N.call('nf_glow_flow_pack', ctypes.addressof(host) + i * nbytes, ctypes.addressof(htab), ctypes.addressof(mtab), hg, mg,
-               D, int(odd))
+    for i, ts in enumerate(steps):
+        htab, mtab = _ptr_table(ts[:L.head]), _ptr_table(ts[L.head:])
+        gh = mgt = None
+        if sinks is not None:
+            gh, mgt = sinks[i][L.ghead], _ptr_table(sinks[i][L.gnet])
+        fam.pack(ctypes.addressof(host) + i * nbytes, ctypes.addressof(htab), ctypes.addressof(mtab), gh,
+                 None if mgt is None else ctypes.addressof(mgt), D, *metas[i])
     table = torch.frombuffer(bytearray(host), dtype=torch.uint8).to(device)
     _GLOW_FLOW_TABLES[key] = table
     _GLOW_FLOW_HOST[table.data_ptr()] = host
     return table
 
 
-class _GlowFlowVec(torch.autograd.Function):
-    """(y, ld) of S consecutive [ActNorm, InvertibleConv1x1, AffineCoupling] steps on (N, D) data: one launch forward, one
-    backward.  tensors: per step the 11 head tensors and the 43 MLP tensors of _GlowStepVec.  Needs the gradient sinks of
-    a GradBucket (the Compose peephole checks)."""
+class _FlowRunVec(torch.autograd.Function):
+    """(y, ld) of S consecutive steps of one family on (N, D) data -- Glow: [ActNorm, InvertibleConv1x1, AffineCoupling], RealNVP:
+    [flow BatchNorm (training, affine=False), AffineCoupling] -- in one launch forward, one backward (or, per_step, S single-step
+    launches each way and one fold).  tensors: per step the fam.layout.n tensors of its step node.  Needs the gradient sinks of a
+    GradBucket (the Compose peephole checks)."""
 
     @staticmethod
-    def forward(ctx, z, ld, odds, training, per_step, *tensors):
-        S = len(odds)
-        per = 11 + 43
-        steps = [(odds[i], tensors[per * i:per * i + 11], tensors[per * i + 11:per * (i + 1)]) for i in range(S)]
-        from .functional import _sinks
-        sinks = [_sinks(*_glow_step_learnables(h, m)) for _, h, m in steps]
+    def forward(ctx, z, ld, fam, metas, training, per_step, *tensors):
+        S, per = len(metas), fam.layout.n
+        steps = [tensors[per * i:per * (i + 1)] for i in range(S)]
+        sinks = [_sinks(*_learnables(fam.layout, ts)) for ts in steps]
         if any(g is None for g in sinks):
-            raise RuntimeError('glow_flow_vec needs direct gradient sinks (GradBucket) for every parameter')
+            raise RuntimeError('%s_flow_vec needs direct gradient sinks (GradBucket) for every parameter' % fam.prefix[3:])
         z = z.contiguous()
         Nrows, D = z.shape
         dev = z.device
-        table = _glow_flow_table(steps, sinks, D, dev)
+        table = _flow_table(fam, metas, steps, sinks, D, dev)
         ys = torch.empty(S, Nrows, D, dtype=torch.float32, device=dev)
-        saves = torch.empty(S, N.header_constant('NF_GLOW_FLOW_SAVE_FLOATS'), dtype=torch.float32, device=dev)
+        saves = torch.empty(S * fam.save_floats(Nrows, D), dtype=torch.float32, device=dev)
         ws = WS.zeros(S * N.header_constant('NF_MLP_WS_FLOATS'), dev)
+        mode = (int(training), ) if fam.training_arg else ()
         ctx.host = _GLOW_FLOW_HOST[table.data_ptr()] if per_step else None      # (kept: the cache may be recycled before backward)
-        if per_step:
-            N.call('nf_glow_flow_steps_fwd', ctypes.addressof(ctx.host), S, N.ptr(z), N.ptr(ys), N.ptr(ld),
-                   N.ptr(saves), N.ptr(ws), Nrows, D, int(training), BN_EPS, BN_MOMENTUM, WN_EPS, N.stream())
+        if per_step:       # one launch per step, the backward's gradient folds deferred to one launch
+            N.call(fam.prefix + '_flow_steps_fwd', ctypes.addressof(ctx.host), S, N.ptr(z), N.ptr(ys), N.ptr(ld), N.ptr(saves),
+                   N.ptr(ws), Nrows, D, *mode, BN_EPS, BN_MOMENTUM, WN_EPS, N.stream())
         else:
-            N.call('nf_glow_flow_vec_fwd', table.data_ptr(), S, N.ptr(z), N.ptr(ys), N.ptr(ld), N.ptr(saves), N.ptr(ws), Nrows, D,
-                   int(training), BN_EPS, BN_MOMENTUM, WN_EPS, N.stream())
+            N.call(fam.prefix + '_flow_vec_fwd', table.data_ptr(), S, N.ptr(z), N.ptr(ys), N.ptr(ld), N.ptr(saves), N.ptr(ws),
+                   Nrows, D, *mode, BN_EPS, BN_MOMENTUM, WN_EPS, N.stream())
         ctx.save_for_backward(z, ys, saves, table)
-        ctx.meta = (S, bool(training), len(tensors), bool(per_step))
+        ctx.meta = (fam, mode, len(tensors))
         ctx.mark_dirty(ld)
         return ys[S - 1], ld
 
     @staticmethod
     def backward(ctx, g_y, g_ld):
-        S, training, n_tensors, per_step = ctx.meta
+        fam, mode, n_tensors = ctx.meta
         z, ys, saves, table = ctx.saved_tensors
+        S = ys.shape[0]
         Nrows, D = z.shape
         dev = z.device
         g_y = g_y.contiguous()
         g_ld = None if g_ld is None else g_ld.contiguous()
         gzs = torch.empty(S, Nrows, D, dtype=torch.float32, device=dev)
         ws = WS.zeros(S * N.header_constant('NF_MLP_WS_FLOATS'), dev)
-        if per_step:
-            rpb = N.header_constant('NF_MLP_ROWS_PER_BLOCK')
-            slabs, rec = _glow_steps_scratch(S, (Nrows + rpb - 1) // rpb, dev)
-            N.call('nf_glow_flow_steps_bwd', ctypes.addressof(ctx.host), table.data_ptr(), S, N.ptr(z),
-                   N.ptr(ys), N.ptr(g_y), _p(g_ld), N.ptr(gzs), N.ptr(saves), 1, N.ptr(ws), N.ptr(slabs), N.ptr(rec), Nrows, D,
-                   int(training), BN_EPS, WN_EPS, N.stream())
+        if ctx.host is not None:
+            slabs, rec = _glow_steps_scratch(S, _row_blocks(Nrows), dev)
+            N.call(fam.prefix + '_flow_steps_bwd', ctypes.addressof(ctx.host), table.data_ptr(), S, N.ptr(z), N.ptr(ys), N.ptr(g_y),
+                   _p(g_ld), N.ptr(gzs), N.ptr(saves), 1, N.ptr(ws), N.ptr(slabs), N.ptr(rec), Nrows, D, *mode, BN_EPS, WN_EPS,
+                   N.stream())
         elif FLOW_DEFER_FOLD:                  # whole-flow launch, every step's gradient fold in ONE launch behind it
-            rpb = N.header_constant('NF_MLP_ROWS_PER_BLOCK')
-            slabs, rec = _glow_steps_scratch(S, (Nrows + rpb - 1) // rpb, dev)
-            N.call('nf_glow_flow_vec_bwd_deferred', table.data_ptr(), S, N.ptr(z), N.ptr(ys), N.ptr(g_y), _p(g_ld), N.ptr(gzs),
-                   N.ptr(saves), 1, N.ptr(ws), N.ptr(slabs), N.ptr(rec), Nrows, D, int(training), BN_EPS, WN_EPS, N.stream())
+            slabs, rec = _glow_steps_scratch(S, fam.regions(Nrows, D), dev)
+            N.call(fam.prefix + '_flow_vec_bwd_deferred', table.data_ptr(), S, N.ptr(z), N.ptr(ys), N.ptr(g_y), _p(g_ld), N.ptr(gzs),
+                   N.ptr(saves), 1, N.ptr(ws), N.ptr(slabs), N.ptr(rec), Nrows, D, *mode, BN_EPS, WN_EPS, N.stream())
         else:
-            N.call('nf_glow_flow_vec_bwd', table.data_ptr(), S, N.ptr(z), N.ptr(ys), N.ptr(g_y), _p(g_ld), N.ptr(gzs), N.ptr(saves),
-                   1, N.ptr(ws), N.ptr(_glow_flow_slabs(dev)), Nrows, D, int(training), BN_EPS, WN_EPS, N.stream())
-        return (gzs[0], g_ld, None, None, None) + (None, ) * n_tensors
+            N.call(fam.prefix + '_flow_vec_bwd', table.data_ptr(), S, N.ptr(z), N.ptr(ys), N.ptr(g_y), _p(g_ld), N.ptr(gzs),
+                   N.ptr(saves), 1, N.ptr(ws), N.ptr(_glow_flow_slabs(dev)), Nrows, D, *mode, BN_EPS, WN_EPS, N.stream())
+        return (gzs[0], g_ld, None, None, None, None) + (None, ) * n_tensors
 
 
-def glow_flow_vec_usable(z, steps):
-    """steps: [(actnorm, conv, coupling)] -- at least two fused-step-capable steps whose parameters all have direct sinks."""
-    from .functional import grad_sink
-    on = _flow_on(z) or _glow_steps_on(z)
-    if not on or len(steps) < 2 or len(steps) > N.header_constant('NF_GLOW_FLOW_MAX_STEPS') or not torch.is_grad_enabled():
+def _flow_run_usable(fam, z, steps, step_ok):
+    if not (_flow_on(z) or _glow_steps_on(z)) or len(steps) < 2 or len(steps) > N.header_constant('NF_GLOW_FLOW_MAX_STEPS') \
+            or not torch.is_grad_enabled():
         return False
-    for a, c, k in steps:
-        if not glow_step_vec_usable(z, k.net):
+    for st in steps:
+        if not step_ok(*st):
             return False
-        head = [a.log_scale, a.bias, c.P, c.L, c.U, c.L_mask, c.U_mask, c.sign_s, c.log_s, k.s_log_scale, k.s_bias]
-        if any(grad_sink(t) is None for t in _glow_step_learnables(head, _mlp_tensors(k.net))):
+        if any(grad_sink(t) is None for t in _learnables(fam.layout, fam.tensors(*st))):
             return False
     return True
 
 
+def _flow_run_vec(fam, z, ld, steps):
+    tensors = [t for st in steps for t in fam.tensors(*st)]
+    metas = tuple(fam.meta(*st) for st in steps)
+    return _FlowRunVec.apply(z, _owned_ld(ld), fam, metas, steps[0][-1].net.training, not _flow_on(z), *tensors)
+
+
+def glow_flow_vec_usable(z, steps):
+    """steps: [(actnorm, conv, coupling)] -- at least two fused-step-capable steps whose parameters all have direct sinks."""
+    return _flow_run_usable(_GLOW_RUN, z, steps, lambda a, c, k: glow_step_vec_usable(z, k.net))
+
+
 def glow_flow_vec(z, ld, steps):
-    from .functional import _owned_ld
-    tensors = []
-    for a, c, k in steps:
-        tensors += [a.log_scale, a.bias, c.P, c.L, c.U, c.L_mask, c.U_mask, c.sign_s, c.log_s, k.s_log_scale, k.s_bias]
-        tensors += _mlp_tensors(k.net)
-    odds = tuple(int(k.odd) for _, _, k in steps)
-    return _GlowFlowVec.apply(z, _owned_ld(ld), odds, steps[0][2].net.training, not _flow_on(z), *tensors)
+    return _flow_run_vec(_GLOW_RUN, z, ld, steps)
 
 
 def glow_flow_nograd_usable(z, steps):
@@ -915,17 +1005,19 @@ def glow_flow_nograd_usable(z, steps):
     return all(a.initialized and glow_step_vec_usable(z, k.net) and k.net.training == training for a, c, k in steps)
 
 
+def _glow_const_table(steps, head, D, device):
+    """records of [(actnorm, conv, coupling)] without gradient tables; head: _glow_head | _glow_inverse_head"""
+    return _flow_table(_GLOW_RUN, tuple(_GLOW_RUN.meta(*st) for st in steps),
+                       [_detached(head(*st) + _mlp_tensors(st[2].net)) for st in steps], None, D, device)
+
+
 def glow_flow_vec_nograd(z, ld, steps):
-    from .functional import _owned_ld
     z = z.contiguous()
     Nrows, D = z.shape
     dev = z.device
     S = len(steps)
     training = bool(steps[0][2].net.training)
-    recs = [(int(k.odd), [t.detach() for t in (a.log_scale, a.bias, c.P, c.L, c.U, c.L_mask, c.U_mask, c.sign_s, c.log_s,
-                                                 k.s_log_scale, k.s_bias)], [t.detach() for t in _mlp_tensors(k.net)])
-            for a, c, k in steps]
-    table = _glow_flow_table(recs, None, D, dev)
+    table = _glow_const_table(steps, _glow_head, D, dev)
     ld = _owned_ld(ld)
     ys = torch.empty(S, Nrows, D, dtype=torch.float32, device=dev)
     saves = torch.empty(S, N.header_constant('NF_GLOW_FLOW_SAVE_FLOATS'), dtype=torch.float32, device=dev)
@@ -938,12 +1030,6 @@ def glow_flow_vec_nograd(z, ld, steps):
 
 # ---- the INVERSE of vector Glow steps (sampling: net.backward), one launch per step or per run --------------------------------
 GLOW_INVERSE = True             # (internal: fused inverse / no-grad launches)
-
-
-def _glow_inverse_head(a, c, k):
-    """the 11 head tensors of _GlowStepVec with the pivots' row-swap matrix in the P slot (nf_glow_step_vec_inv)"""
-    return [a.log_scale, a.bias, c._pivot_matrix().contiguous(), c.L, c.U, c.L_mask, c.U_mask, c.sign_s, c.log_s, k.s_log_scale,
-            k.s_bias]
 
 
 def glow_inverse_usable(y, steps):
@@ -974,9 +1060,7 @@ def glow_flow_vec_inverse(y, ld, steps):
         ws = WS.zeros(S * nws, dev) if training else torch.empty(nws, dtype=torch.float32, device=dev)
         saves = torch.empty(S, nsave, dtype=torch.float32, device=dev)
         if one_launch:
-            recs = [(int(k.odd), [t.detach() for t in _glow_inverse_head(a, c, k)], [t.detach() for t in _mlp_tensors(k.net)])
-                    for a, c, k in steps]
-            table = _glow_flow_table(recs, None, D, dev)
+            table = _glow_const_table(steps, _glow_inverse_head, D, dev)
             zs = torch.empty(2, Nrows, D, dtype=torch.float32, device=dev)
             N.call('nf_glow_flow_vec_inv', table.data_ptr(), S, N.ptr(y), N.ptr(zs), N.ptr(ld), N.ptr(saves),
                    N.ptr(ws), Nrows, D, int(training), BN_EPS, BN_MOMENTUM, WN_EPS, N.stream())
@@ -985,96 +1069,13 @@ def glow_flow_vec_inverse(y, ld, steps):
         for i in range(S - 1, -1, -1):
             a, c, k = steps[i]
             z = torch.empty_like(cur)
-            htab = _ptr_table([t.detach() for t in _glow_inverse_head(a, c, k)])
-            mtab = _ptr_table([t.detach() for t in _mlp_tensors(k.net)])
+            htab = _ptr_table(_detached(_glow_inverse_head(a, c, k)))
+            mtab = _ptr_table(_detached(_mlp_tensors(k.net)))
             N.call('nf_glow_step_vec_inv', N.ptr(cur), N.ptr(z), N.ptr(ld), ctypes.addressof(htab), ctypes.addressof(mtab),
                    N.ptr(saves[i]), N.ptr(ws[i * nws:(i + 1) * nws]) if training else N.ptr(ws), Nrows, D, int(k.odd), int(training),
                    BN_EPS, BN_MOMENTUM, WN_EPS, N.stream())
             cur = z
         return cur, ld
-
-
-def _realnvp_step_learnables(head, mlp):
-    nl, nb = 6, 5
-    return [head[6], head[7]] + list(mlp[:3 * nl]) + [t for j in range(nb) for t in mlp[3 * nl + 5 * j:3 * nl + 5 * j + 2]]
-
-
-def _realnvp_flow_table(steps, sinks, D, device):
-    """steps: [(odd, flow_bn_eps, flow_bn_momentum, 8 head tensors, 43 MLP tensors)]; sinks: per step the 30 gradient buffers."""
-    key = ('realnvp', device, D, tuple((int(o), float(e), float(m)) for o, e, m, _, _ in steps),
-           tuple(t.data_ptr() for _, _, _, h, m in steps for t in list(h) + list(m)), tuple(t.data_ptr() for g in sinks for t in g))
-    hit = _GLOW_FLOW_TABLES.get(key)
-    if hit is not None:
-        return hit
-    nbytes = int(N.load().nf_glow_flow_step_bytes())
-    host = (ctypes.c_ubyte * (nbytes * len(steps)))()
-    for i, (odd, eps, mom, head, mlp) in enumerate(steps):
-        htab, mtab, mgt = _ptr_table(head), _ptr_table(mlp), _ptr_table(sinks[i][2:])
-        N.call('nf_realnvp_flow_pack', ctypes.addressof(host) + i * nbytes, ctypes.addressof(htab), ctypes.addressof(mtab),
-               N.ptr(sinks[i][0]), N.ptr(sinks[i][1]), ctypes.addressof(mgt), D, int(odd), float(eps), float(mom))
-    table = torch.frombuffer(bytearray(host), dtype=torch.uint8).to(device)
-    _GLOW_FLOW_TABLES[key] = table
-    _GLOW_FLOW_HOST[table.data_ptr()] = host
-    return table
-
-
-class _RealNVPFlowVec(torch.autograd.Function):
-    """S consecutive [flow BatchNorm (training, affine=False), AffineCoupling] steps on (N, D) data: one launch per direction.
-    tensors: per step the 8 head tensors and the 43 MLP tensors of _RealNVPStepVec."""
-
-    @staticmethod
-    def forward(ctx, z, ld, metas, per_step, *tensors):
-        S = len(metas)
-        per = 8 + 43
-        steps = [metas[i] + (tensors[per * i:per * i + 8], tensors[per * i + 8:per * (i + 1)]) for i in range(S)]
-        from .functional import _sinks
-        sinks = [_sinks(*_realnvp_step_learnables(h, m)) for _, _, _, h, m in steps]
-        if any(g is None for g in sinks):
-            raise RuntimeError('realnvp_flow_vec needs direct gradient sinks (GradBucket) for every parameter')
-        z = z.contiguous()
-        Nrows, D = z.shape
-        dev = z.device
-        table = _realnvp_flow_table(steps, sinks, D, dev)
-        ys = torch.empty(S, Nrows, D, dtype=torch.float32, device=dev)
-        # (S statistics records, then -- for the shapes the one-workgroup kernels take -- the stash of BatchNorm inputs: the library says how much)
-        saves = torch.empty(S * int(N.load().nf_realnvp_flow_save_floats(Nrows, D)), dtype=torch.float32, device=dev)
-        ws = WS.zeros(S * N.header_constant('NF_MLP_WS_FLOATS'), dev)
-        ctx.host = _GLOW_FLOW_HOST[table.data_ptr()] if per_step else None
-        if per_step:       # one launch per step, the backward's gradient folds deferred to one launch (as for the Glow steps)
-            N.call('nf_realnvp_flow_steps_fwd', ctypes.addressof(ctx.host), S, N.ptr(z), N.ptr(ys), N.ptr(ld), N.ptr(saves), N.ptr(ws),
-                   Nrows, D, BN_EPS, BN_MOMENTUM, WN_EPS, N.stream())
-        else:
-            N.call('nf_realnvp_flow_vec_fwd', table.data_ptr(), S, N.ptr(z), N.ptr(ys), N.ptr(ld), N.ptr(saves), N.ptr(ws), Nrows, D,
-                   BN_EPS, BN_MOMENTUM, WN_EPS, N.stream())
-        ctx.save_for_backward(z, ys, saves, table)
-        ctx.meta = (S, len(tensors))
-        ctx.mark_dirty(ld)
-        return ys[S - 1], ld
-
-    @staticmethod
-    def backward(ctx, g_y, g_ld):
-        S, n_tensors = ctx.meta
-        z, ys, saves, table = ctx.saved_tensors
-        Nrows, D = z.shape
-        dev = z.device
-        g_y = g_y.contiguous()
-        g_ld = None if g_ld is None else g_ld.contiguous()
-        gzs = torch.empty(S, Nrows, D, dtype=torch.float32, device=dev)
-        ws = WS.zeros(S * N.header_constant('NF_MLP_WS_FLOATS'), dev)
-        if ctx.host is not None:
-            rpb = N.header_constant('NF_MLP_ROWS_PER_BLOCK')
-            slabs, rec = _glow_steps_scratch(S, (Nrows + rpb - 1) // rpb, dev)
-            N.call('nf_realnvp_flow_steps_bwd', ctypes.addressof(ctx.host), table.data_ptr(), S, N.ptr(z), N.ptr(ys), N.ptr(g_y),
-                   _p(g_ld), N.ptr(gzs), N.ptr(saves), 1, N.ptr(ws), N.ptr(slabs), N.ptr(rec), Nrows, D, BN_EPS, WN_EPS, N.stream())
-        elif FLOW_DEFER_FOLD:
-            regions = int(N.load().nf_realnvp_flow_bwd_regions(Nrows, D))      # (the one-workgroup kernel leaves its own number of partials)
-            slabs, rec = _glow_steps_scratch(S, regions, dev)
-            N.call('nf_realnvp_flow_vec_bwd_deferred', table.data_ptr(), S, N.ptr(z), N.ptr(ys), N.ptr(g_y), _p(g_ld), N.ptr(gzs),
-                   N.ptr(saves), 1, N.ptr(ws), N.ptr(slabs), N.ptr(rec), Nrows, D, BN_EPS, WN_EPS, N.stream())
-        else:
-            N.call('nf_realnvp_flow_vec_bwd', table.data_ptr(), S, N.ptr(z), N.ptr(ys), N.ptr(g_y), _p(g_ld), N.ptr(gzs), N.ptr(saves),
-                   1, N.ptr(ws), N.ptr(_glow_flow_slabs(dev)), Nrows, D, BN_EPS, WN_EPS, N.stream())
-        return (gzs[0], g_ld, None, None) + (None, ) * n_tensors
 
 
 def _flow_on(z):
@@ -1091,27 +1092,11 @@ def _glow_steps_on(z):
 
 def realnvp_flow_vec_usable(z, steps):
     """steps: [(flow BatchNorm, AffineCoupling)] -- at least two fused-step-capable steps, every parameter with a direct sink."""
-    from .functional import grad_sink
-    if not (_flow_on(z) or _glow_steps_on(z)) or len(steps) < 2 or len(steps) > N.header_constant('NF_GLOW_FLOW_MAX_STEPS') \
-            or not torch.is_grad_enabled():
-        return False
-    for bn, k in steps:
-        if not realnvp_step_vec_usable(z, bn, k.net):
-            return False
-        head = [bn.log_gamma, bn.beta, bn.batch_mean, bn.batch_var, bn.running_mean, bn.running_var, k.s_log_scale, k.s_bias]
-        if any(grad_sink(t) is None for t in _realnvp_step_learnables(head, _mlp_tensors(k.net))):
-            return False
-    return True
+    return _flow_run_usable(_REALNVP_RUN, z, steps, lambda bn, k: realnvp_step_vec_usable(z, bn, k.net))
 
 
 def realnvp_flow_vec(z, ld, steps):
-    from .functional import _owned_ld
-    tensors, metas = [], []
-    for bn, k in steps:
-        tensors += [bn.log_gamma, bn.beta, bn.batch_mean, bn.batch_var, bn.running_mean, bn.running_var, k.s_log_scale, k.s_bias]
-        tensors += _mlp_tensors(k.net)
-        metas.append((int(k.odd), float(bn.eps), float(bn.momentum)))
-    return _RealNVPFlowVec.apply(z, _owned_ld(ld), tuple(metas), not _flow_on(z), *tensors)
+    return _flow_run_vec(_REALNVP_RUN, z, ld, steps)
 
 
 FBN_RUNNING, FBN_BATCH_BUFFERS = -1.0, -2.0              # include/nfhip.h: NF_FBN_RUNNING, NF_FBN_BATCH_BUFFERS
@@ -1125,9 +1110,7 @@ def _maf_struct_ok(z, bn, ar):
 
 
 def _maf_tables(bn, ar, ms, mt):
-    head = [bn.log_gamma, bn.beta, bn.batch_mean, bn.batch_var, bn.running_mean, bn.running_var, ar.perm, ar.s_log_scale, ar.s_bias]
-    made = _made_tensors(ar.net_s, ms) + _made_tensors(ar.net_t, mt)
-    return _ptr_table([t.detach() for t in head]), _ptr_table([t.detach() for t in made])
+    return _ptr_table(_detached(_maf_head(bn, ar))), _ptr_table(_detached(_made_tensors(ar.net_s, ms) + _made_tensors(ar.net_t, mt)))
 
 
 def maf_step_eval_usable(z, bn, ar):
@@ -1136,7 +1119,6 @@ def maf_step_eval_usable(z, bn, ar):
 
 def maf_step_eval(z, ld, bn, ar):
     """[flow BatchNorm, AutoregressiveTransfrom] in evaluation mode under no_grad: one launch, no grid exchange"""
-    from .functional import _owned_ld
     z = z.contiguous()
     Nrows, D = z.shape
     ms = ar.net_s.draw_masks(z.device)                       # same RNG order as the reference: s-net, then t-net
@@ -1181,23 +1163,8 @@ def maf_step_inverse(y, ld, bn, ar):
 
 def _realnvp_const_table(steps, mode, D, device):
     """records of [(flow BatchNorm, AffineCoupling)] whose flow BatchNorm reads constants (mode: FBN_RUNNING | FBN_BATCH_BUFFERS)"""
-    heads = [[t.detach() for t in (bn.log_gamma, bn.beta, bn.batch_mean, bn.batch_var, bn.running_mean, bn.running_var,
-                                   k.s_log_scale, k.s_bias)] for bn, k in steps]
-    mlps = [[t.detach() for t in _mlp_tensors(k.net)] for _, k in steps]
-    key = ('realnvp-const', mode, device, D, tuple(int(k.odd) for _, k in steps),
-           tuple(t.data_ptr() for h, m in zip(heads, mlps) for t in h + m))
-    hit = _GLOW_FLOW_TABLES.get(key)
-    if hit is not None:
-        return hit
-    nbytes = int(N.load().nf_glow_flow_step_bytes())
-    host = (ctypes.c_ubyte * (nbytes * len(steps)))()
-    for i, (bn, k) in enumerate(steps):
-        htab, mtab = _ptr_table(heads[i]), _ptr_table(mlps[i])
-        N.call('nf_realnvp_flow_pack', ctypes.addressof(host) + i * nbytes, ctypes.addressof(htab), ctypes.addressof(mtab), None, None,
-               None, D, int(k.odd), float(bn.eps), float(mode))
-    table = torch.frombuffer(bytearray(host), dtype=torch.uint8).to(device)
-    _GLOW_FLOW_TABLES[key] = table
-    return table
+    return _flow_table(_REALNVP_RUN, tuple((int(k.odd), float(bn.eps), float(mode)) for bn, k in steps),
+                       [_detached(_realnvp_step_tensors(bn, k)) for bn, k in steps], None, D, device)
 
 
 def _realnvp_const_usable(z, steps):
@@ -1214,7 +1181,6 @@ def realnvp_eval_usable(z, steps):
 
 
 def realnvp_flow_vec_eval(z, ld, steps):
-    from .functional import _owned_ld
     z = z.contiguous()
     Nrows, D = z.shape
     dev = z.device
@@ -1256,9 +1222,8 @@ def realnvp_flow_vec_inverse(y, ld, steps):
         for i in range(S - 1, -1, -1):
             bn, k = steps[i]
             z = torch.empty_like(cur)
-            htab = _ptr_table([t.detach() for t in (bn.log_gamma, bn.beta, bn.batch_mean, bn.batch_var, bn.running_mean,
-                                                    bn.running_var, k.s_log_scale, k.s_bias)])
-            mtab = _ptr_table([t.detach() for t in _mlp_tensors(k.net)])
+            htab = _ptr_table(_detached(_realnvp_head(bn, k)))
+            mtab = _ptr_table(_detached(_mlp_tensors(k.net)))
             N.call('nf_realnvp_step_vec_inv', N.ptr(cur), N.ptr(z), N.ptr(ld), ctypes.addressof(htab), ctypes.addressof(mtab),
                    N.ptr(saves[i]), N.ptr(ws[i * nws:(i + 1) * nws]), Nrows, D, int(k.odd), int(training), BN_EPS, BN_MOMENTUM, WN_EPS,
                    N.stream())
@@ -1307,7 +1272,6 @@ class _FlowppCouplingVec(torch.autograd.Function):
                    N.SPLIT_1D, int(odd), Nrows, D, 1, 1, N.stream())
         ctx.save_for_backward(z, params, *tensors)
         ctx.meta = (K, float(eps), int(odd), F_, n_post)
-        from .functional import _sinks
         ctx.sinks_ac = _sinks(a, c)
         ctx.sinks_net = _sinks(*ts)
         ctx.sinks_post = _sinks(*post) if n_post else None
@@ -1388,7 +1352,6 @@ def flowpp_post_actnorm_usable(z, coupling, actnorm):
 def flowpp_coupling_vec(z, ld, coupling, post=None):
     """MixLogAttnCoupling.forward on (N, D) data with the fused conditioner (see flowpp_cond_fusable); post = the next flow
     step's (initialised) ActNorm, applied in the same launches when flowpp_post_actnorm_usable."""
-    from .functional import _owned_ld
     ts, F_ = _flowpp_tensors(coupling.net)
     extra = () if post is None else (post.log_scale, post.bias)
     return _FlowppCouplingVec.apply(z, _owned_ld(ld), coupling.n_mixtures, coupling.logit_eps, int(coupling.odd), F_,
@@ -1405,33 +1368,8 @@ def maf_step_usable(z, bn, ar):
             and 1 < z.shape[0] <= N.maf_max_rows())
 
 
-_MAF_SLABS = {}
-
-
 def _maf_slabs(device):
-    t = _MAF_SLABS.get(device)
-    if t is None:
-        t = _MAF_SLABS[device] = torch.empty(N.header_constant('NF_MAF_BWD_SLAB_FLOATS'), dtype=torch.float32, device=device)
-    return t
-
-
-def _made_tensors(net, masks):
-    ts = []
-    for l in range(net.num_hidden + 1):
-        ts += [net.weights[l], masks[l], net.biases[l]]
-    for bn in net.bnorms:
-        ts += [bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked]
-    return ts
-
-
-def _made_learnables(ts):
-    """(weight, bias) * 4 then (gamma, beta) * 3 of one net's 27-tensor list."""
-    out = []
-    for l in range(4):
-        out += [ts[3 * l], ts[3 * l + 2]]
-    for j in range(3):
-        out += [ts[12 + 5 * j], ts[12 + 5 * j + 1]]
-    return out
+    return _device_scratch('NF_MAF_BWD_SLAB_FLOATS', device)
 
 
 class _MAFStepVec(torch.autograd.Function):
@@ -1440,7 +1378,7 @@ class _MAFStepVec(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, ld, bn_eps, bn_momentum, *tensors):
-        head, made = tensors[:9], tensors[9:]
+        head, made = tensors[:_MAF.head], tensors[_MAF.head:]
         z = z.contiguous()
         Nrows, D = z.shape
         y = torch.empty_like(z)
@@ -1450,50 +1388,37 @@ class _MAFStepVec(torch.autograd.Function):
         N.call('nf_maf_step_fwd', N.ptr(z), N.ptr(y), N.ptr(ld), ctypes.addressof(htab), ctypes.addressof(mtab), N.ptr(save),
                N.ptr(ws), Nrows, D, float(bn_eps), float(bn_momentum), BN_EPS, N.stream())
         ctx.save_for_backward(z, save, *tensors)
-        from .functional import _sinks
-        learn = _made_learnables(made[:27]) + _made_learnables(made[27:]) + [head[7], head[8]]
-        ctx.sinks = _sinks(*learn)
+        ctx.sinks = _sinks(*_learnables(_MAF, tensors))
         ctx.mark_dirty(ld)
         return y, ld
 
     @staticmethod
     def backward(ctx, g_y, g_ld):
         z, save, *tensors = ctx.saved_tensors
-        head, made = tensors[:9], tensors[9:]
+        head, made = tensors[:_MAF.head], tensors[_MAF.head:]
         Nrows, D = z.shape
         dev = z.device
         g_y = g_y.contiguous()
         g_ld = None if g_ld is None else g_ld.contiguous()
-        learn = _made_learnables(made[:27]) + _made_learnables(made[27:]) + [head[7], head[8]]
         direct = ctx.sinks is not None
-        dst = ctx.sinks if direct else [torch.zeros_like(t) for t in learn]      # the kernel accumulates by atomics
+        dst = ctx.sinks if direct else [torch.zeros_like(t) for t in _learnables(_MAF, tensors)]      # the kernel accumulates by atomics
         g_z = torch.empty_like(z)
         ws = WS.zeros(N.header_constant('NF_MAF_WS_FLOATS'), dev)
-        htab, mtab, gtab = _ptr_table(head), _ptr_table(made), _ptr_table(dst[:28])
+        htab, mtab, gtab = _ptr_table(head), _ptr_table(made), _ptr_table(dst[_MAF.gnet])
+        g_scale, g_bias = dst[_MAF.ghead]
         N.call('nf_maf_step_bwd', N.ptr(z), N.ptr(g_y), _p(g_ld), N.ptr(g_z), ctypes.addressof(htab), ctypes.addressof(mtab),
-               N.ptr(save), ctypes.addressof(gtab), N.ptr(dst[28]), N.ptr(dst[29]), N.ptr(ws), N.ptr(_maf_slabs(dev)), Nrows, D,
+               N.ptr(save), ctypes.addressof(gtab), N.ptr(g_scale), N.ptr(g_bias), N.ptr(ws), N.ptr(_maf_slabs(dev)), Nrows, D,
                N.stream())
         if direct:
             return (g_z, g_ld, None, None) + (None, ) * len(tensors)
-        gh = [None] * 7 + [dst[28], dst[29]]
-        gm = []
-        for n in range(2):
-            d = dst[14 * n:14 * n + 14]
-            for l in range(4):
-                gm += [d[2 * l], None, d[2 * l + 1]]
-            for j in range(3):
-                gm += [d[8 + 2 * j], d[8 + 2 * j + 1], None, None, None]
-        return (g_z, g_ld, None, None) + tuple(gh) + tuple(gm)
+        return (g_z, g_ld, None, None) + _place_grads(_MAF, dst)
 
 
 def maf_step_vec(z, ld, bn, ar):
     """[flow BatchNorm ``bn`` (training, affine=False), AutoregressiveTransfrom ``ar``] on (N, D) data, fused."""
-    from .functional import _owned_ld
     ms = ar.net_s.draw_masks(z.device)                       # same RNG order as the reference: s-net, then t-net
     mt = ar.net_t.draw_masks(z.device)
-    head = [bn.log_gamma, bn.beta, bn.batch_mean, bn.batch_var, bn.running_mean, bn.running_var, ar.perm, ar.s_log_scale,
-            ar.s_bias]
-    return _MAFStepVec.apply(z, _owned_ld(ld), bn.eps, bn.momentum, *(head + _made_tensors(ar.net_s, ms) + _made_tensors(ar.net_t, mt)))
+    return _MAFStepVec.apply(z, _owned_ld(ld), bn.eps, bn.momentum, *_maf_step_tensors(bn, ar, ms, mt))
 
 
 # a run of MAF steps as ONE autograd node: the step launches of _MAFStepVec, the backward's in deferred-fold mode -- every step
@@ -1502,17 +1427,9 @@ MAF_FLOW = _os.environ.get('NF_MAF_FLOW', '1') != '0'
 
 
 def _maf_steps_scratch(S, blocks, device):
-    key = ('maf_steps', device)
-    n = S * blocks * N.header_constant('NF_MAF_SLAB_WG_FLOATS')
-    m = S * blocks * N.header_constant('NF_MAF_HEAD_REC_WG')
-    t = _MAF_SLABS.get(key)
-    if t is None or t[0].numel() < n or t[1].numel() < m:
-        t = _MAF_SLABS[key] = (torch.empty(n, dtype=torch.float32, device=device), torch.empty(m, dtype=torch.float32, device=device))
-    return t
-
-
-def _maf_step_learnables(head, made):
-    return _made_learnables(made[:27]) + _made_learnables(made[27:]) + [head[7], head[8]]
+    """as _glow_steps_scratch: the pair reaches captured train steps the same way"""
+    return _scratch_pair('maf_steps', S * blocks * N.header_constant('NF_MAF_SLAB_WG_FLOATS'),
+                         S * blocks * N.header_constant('NF_MAF_HEAD_REC_WG'), device)
 
 
 class _MAFFlowVec(torch.autograd.Function):
@@ -1521,8 +1438,7 @@ class _MAFFlowVec(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, ld, metas, *tensors):
-        S, per = len(metas), 9 + 54
-        from .functional import _sinks
+        S, per = len(metas), _MAF.n
         z = z.contiguous()
         Nrows, D = z.shape
         dev = z.device
@@ -1532,12 +1448,12 @@ class _MAFFlowVec(torch.autograd.Function):
         ws = WS.zeros(S * nws, dev)
         sinks = []
         for i in range(S):
-            head, made = tensors[per * i:per * i + 9], tensors[per * i + 9:per * (i + 1)]
-            g = _sinks(*_maf_step_learnables(head, made))
+            step = tensors[per * i:per * (i + 1)]
+            g = _sinks(*_learnables(_MAF, step))
             if g is None:
                 raise RuntimeError('maf_flow_vec needs direct gradient sinks (GradBucket) for every parameter')
             sinks.append(g)
-            htab, mtab = _ptr_table(head), _ptr_table(made)
+            htab, mtab = _ptr_table(step[:_MAF.head]), _ptr_table(step[_MAF.head:])
             N.call('nf_maf_step_fwd', N.ptr(z) if i == 0 else N.ptr(ys[i - 1]), N.ptr(ys[i]), N.ptr(ld), ctypes.addressof(htab),
                    ctypes.addressof(mtab), N.ptr(saves[i]), N.ptr(ws[i * nws:(i + 1) * nws]), Nrows, D, float(metas[i][0]),
                    float(metas[i][1]), BN_EPS, N.stream())
@@ -1549,7 +1465,7 @@ class _MAFFlowVec(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_y, g_ld):
         z, ys, saves, *tensors = ctx.saved_tensors
-        S, per = ys.shape[0], 9 + 54
+        S, per = ys.shape[0], _MAF.n
         Nrows, D = z.shape
         dev = z.device
         g_y = g_y.contiguous()
@@ -1560,21 +1476,20 @@ class _MAFFlowVec(torch.autograd.Function):
         blocks = -(-Nrows // N.header_constant('NF_MAF_ROWS_PER_BLOCK'))
         nsl, nrec = blocks * N.header_constant('NF_MAF_SLAB_WG_FLOATS'), blocks * N.header_constant('NF_MAF_HEAD_REC_WG')
         slabs, rec = _maf_steps_scratch(S, blocks, dev)
-        all_made, all_grads, all_a, all_c = [], [], [], []
         for i in range(S - 1, -1, -1):
-            head, made = tensors[per * i:per * i + 9], tensors[per * i + 9:per * (i + 1)]
-            dst = ctx.sinks[i]
-            htab, mtab, gtab = _ptr_table(head), _ptr_table(made), _ptr_table(dst[:28])
+            step = tensors[per * i:per * (i + 1)]
+            htab, mtab, gtab = _ptr_table(step[:_MAF.head]), _ptr_table(step[_MAF.head:]), _ptr_table(ctx.sinks[i][_MAF.gnet])
             N.call('nf_maf_step_bwd_partial', N.ptr(z) if i == 0 else N.ptr(ys[i - 1]), N.ptr(g_y) if i == S - 1 else N.ptr(gzs[i + 1]),
                    _p(g_ld), N.ptr(gzs[i]), ctypes.addressof(htab), ctypes.addressof(mtab), N.ptr(saves[i]), ctypes.addressof(gtab),
                    N.ptr(ws[i * nws:(i + 1) * nws]), N.ptr(slabs[i * nsl:(i + 1) * nsl]), N.ptr(rec[i * nrec:(i + 1) * nrec]), Nrows, D,
                    N.stream())
+        all_made, all_grads, all_a, all_c = [], [], [], []
         for i in range(S):
-            head, made = tensors[per * i:per * i + 9], tensors[per * i + 9:per * (i + 1)]
-            all_made += list(made)
-            all_grads += list(ctx.sinks[i][:28])
-            all_a.append(ctx.sinks[i][28])
-            all_c.append(ctx.sinks[i][29])
+            all_made += tensors[per * i + _MAF.head:per * (i + 1)]
+            all_grads += ctx.sinks[i][_MAF.gnet]
+            g_scale, g_bias = ctx.sinks[i][_MAF.ghead]
+            all_a.append(g_scale)
+            all_c.append(g_bias)
         pm, pg, pa, pc = _ptr_table(all_made), _ptr_table(all_grads), _ptr_table(all_a), _ptr_table(all_c)
         N.call('nf_maf_fold_all', ctypes.addressof(pm), ctypes.addressof(pg), ctypes.addressof(pa), ctypes.addressof(pc), S, N.ptr(slabs),
                N.ptr(rec), blocks, D, N.stream())
@@ -1583,27 +1498,22 @@ class _MAFFlowVec(torch.autograd.Function):
 
 def maf_flow_vec_usable(z, steps):
     """steps: [(flow BatchNorm, AutoregressiveTransfrom)] -- at least two fused-step-capable steps, every parameter with a sink."""
-    from .functional import grad_sink
     if not MAF_FLOW or len(steps) < 2 or not torch.is_grad_enabled():
         return False
     for bn, ar in steps:
         if not maf_step_usable(z, bn, ar):
             return False
-        ps = [p for net in (ar.net_s, ar.net_t) for p in list(net.weights) + list(net.biases)]
-        ps += [t for net in (ar.net_s, ar.net_t) for b in net.bnorms for t in (b.weight, b.bias)] + [ar.s_log_scale, ar.s_bias]
-        if any(grad_sink(t) is None for t in ps):
+        if any(grad_sink(t) is None for t in _learnables(_MAF, _maf_step_tensors(bn, ar))):
             return False
     return True
 
 
 def maf_flow_vec(z, ld, steps):
-    from .functional import _owned_ld
     tensors, metas = [], []
     for bn, ar in steps:
         ms = ar.net_s.draw_masks(z.device)                   # same RNG order as the reference: per step s-net, then t-net
         mt = ar.net_t.draw_masks(z.device)
-        tensors += [bn.log_gamma, bn.beta, bn.batch_mean, bn.batch_var, bn.running_mean, bn.running_var, ar.perm, ar.s_log_scale,
-                    ar.s_bias] + _made_tensors(ar.net_s, ms) + _made_tensors(ar.net_t, mt)
+        tensors += _maf_step_tensors(bn, ar, ms, mt)
         metas.append((float(bn.eps), float(bn.momentum)))
     return _MAFFlowVec.apply(z, _owned_ld(ld), tuple(metas), *tensors)
 
@@ -1621,7 +1531,7 @@ class _RealNVPStepVec(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, ld, odd, bn_eps, bn_momentum, *tensors):
-        head, mlp = tensors[:8], tensors[8:]
+        head, mlp = tensors[:_REALNVP.head], tensors[_REALNVP.head:]
         z = z.contiguous()
         Nrows, D = z.shape
         y = torch.empty_like(z)
@@ -1633,46 +1543,35 @@ class _RealNVPStepVec(torch.autograd.Function):
                N.stream())
         ctx.save_for_backward(z, save, *tensors)
         ctx.odd = int(odd)
-        from .functional import _sinks
-        nl, nb = 6, 5
-        learn = [head[6], head[7]] + list(mlp[:3 * nl]) + [t for j in range(nb) for t in mlp[3 * nl + 5 * j:3 * nl + 5 * j + 2]]
-        ctx.sinks = _sinks(*learn)
+        ctx.sinks = _sinks(*_learnables(_REALNVP, tensors))
         ctx.mark_dirty(ld)
         return y, ld
 
     @staticmethod
     def backward(ctx, g_y, g_ld):
-        nl, nb = 6, 5
         z, save, *tensors = ctx.saved_tensors
-        head, mlp = tensors[:8], tensors[8:]
+        head, mlp = tensors[:_REALNVP.head], tensors[_REALNVP.head:]
         Nrows, D = z.shape
         dev = z.device
         g_y = g_y.contiguous()
         g_ld = None if g_ld is None else g_ld.contiguous()
-        learn = [head[6], head[7]] + list(mlp[:3 * nl]) + [t for j in range(nb) for t in mlp[3 * nl + 5 * j:3 * nl + 5 * j + 2]]
         direct = ctx.sinks is not None
-        dst = ctx.sinks if direct else [torch.empty_like(t) for t in learn]
+        dst = ctx.sinks if direct else [torch.empty_like(t) for t in _learnables(_REALNVP, tensors)]
         g_z = torch.empty_like(z)
         ws = WS.zeros(N.header_constant('NF_MLP_WS_FLOATS'), dev)
-        htab, mtab, mg = _ptr_table(head), _ptr_table(mlp), _ptr_table(dst[2:])
+        htab, mtab, mg = _ptr_table(head), _ptr_table(mlp), _ptr_table(dst[_REALNVP.gnet])
+        g_scale, g_bias = dst[_REALNVP.ghead]
         N.call('nf_realnvp_step_vec_bwd', N.ptr(z), N.ptr(g_y), _p(g_ld), N.ptr(g_z), ctypes.addressof(htab),
-               ctypes.addressof(mtab), N.ptr(save), N.ptr(dst[0]), N.ptr(dst[1]), ctypes.addressof(mg), int(direct), N.ptr(ws),
+               ctypes.addressof(mtab), N.ptr(save), N.ptr(g_scale), N.ptr(g_bias), ctypes.addressof(mg), int(direct), N.ptr(ws),
                N.ptr(_mlp_slabs(dev)), Nrows, D, ctx.odd, BN_EPS, WN_EPS, N.stream())
         if direct:
             return (g_z, g_ld, None, None, None) + (None, ) * len(tensors)
-        gh = [None] * 6 + [dst[0], dst[1]]
-        gm = list(dst[2:2 + 3 * nl])
-        for j in range(nb):
-            gm += [dst[2 + 3 * nl + 2 * j], dst[2 + 3 * nl + 2 * j + 1], None, None, None]
-        return (g_z, g_ld, None, None, None) + tuple(gh) + tuple(gm)
+        return (g_z, g_ld, None, None, None) + _place_grads(_REALNVP, dst)
 
 
 def realnvp_step_vec(z, ld, bn, coupling):
     """[flow BatchNorm ``bn`` (training, affine=False), AffineCoupling ``coupling``] on (N, D) data, fused."""
-    from .functional import _owned_ld
-    head = [bn.log_gamma, bn.beta, bn.batch_mean, bn.batch_var, bn.running_mean, bn.running_var, coupling.s_log_scale,
-            coupling.s_bias]
-    return _RealNVPStepVec.apply(z, _owned_ld(ld), int(coupling.odd), bn.eps, bn.momentum, *(head + _mlp_tensors(coupling.net)))
+    return _RealNVPStepVec.apply(z, _owned_ld(ld), int(coupling.odd), bn.eps, bn.momentum, *_realnvp_step_tensors(bn, coupling))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1695,7 +1594,6 @@ class _WeightNormMulti(torch.autograd.Function):
             N.call('nf_weight_norm_fwd', ctypes.addressof(arr), len(descs), float(eps), N.stream())
         ctx.save_for_backward(*tensors)
         ctx.eps = float(eps)
-        from .functional import _sinks
         ctx.sinks = _sinks(*tensors)
         from .fused_conv import CONV_DEFER
         CONV_DEFER.arm(outs)                      # consumers may hand back gradients that are filled when backward() flushes
@@ -1775,7 +1673,6 @@ class _PLUWeightsMulti(torch.autograd.Function):
         _plu_launch('nf_invconv_weight_fwd_multi', descs)
         ctx.save_for_backward(*tensors)
         ctx.holder = holder
-        from .functional import _sinks
         ctx.sinks = [_sinks(tensors[7 * i + 1], tensors[7 * i + 2], tensors[7 * i + 6]) for i in range(n)]
         return tuple(Ws)
 
@@ -1784,7 +1681,6 @@ class _PLUWeightsMulti(torch.autograd.Function):
         tensors = ctx.saved_tensors
         n = len(tensors) // 7
         holder = ctx.holder
-        from .functional import flush_head_params
         flush_head_params(holder)                 # the heads' deferred parameter gradients fill g_Ws
         descs, grads = [], [None]
         for i in range(n):
@@ -1809,7 +1705,6 @@ def plu_weights_all(convs):
     backward reads) for the forward pass under way."""
     if not convs:
         return
-    from .functional import PluHolder
     holder = PluHolder(len(convs))
     tensors = []
     for c in convs:

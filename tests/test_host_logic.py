@@ -135,6 +135,84 @@ def test_flow_table_cache_is_bounded_and_keeps_pinned_entries(pkg):
     assert tables[0].data_ptr() not in cache.host and tables[1].data_ptr() in cache.host
 
 
+def _first_step_cases(pkg, fused):
+    """[(layout, tensor list of the first flow step, wanted length, wanted learnables)] of Glow / RealNVP / MAF on (2,) data"""
+    cfg = NS(layers=2, mixtures=None)
+    glow, rnvp, maf = (getattr(pkg, c)((2, ), '2d', cfg).net.layers for c in ('Glow', 'RealNVP', 'MAF'))
+    return [(fused._GLOW, fused._glow_step_tensors(*glow[:3]), 54, 35), (fused._REALNVP, fused._realnvp_step_tensors(*rnvp[:2]), 51, 30),
+            (fused._MAF, fused._maf_step_tensors(*maf[:2]), 63, 30)], maf[1]
+
+
+def test_step_layouts_name_exactly_the_learnable_tensors_in_gradient_table_order(pkg):
+    """fused._learnables: per family the tensors with requires_grad, by identity, in the order of the C ABI's gradient tables (Glow /
+    RealNVP: list order; MAF: net s, net t, then s_log_scale, s_bias); the index lists are the header's contract, written out."""
+    import importlib
+    fused = importlib.import_module(pkg.__name__ + '.fused')
+    mlp = tuple(range(18)) + (18, 19, 23, 24, 28, 29, 33, 34, 38, 39)
+    made = (0, 2, 3, 5, 6, 8, 9, 11, 12, 13, 17, 18, 22, 23)
+    assert fused._MLP.learn == mlp and fused._MLP.n == 43
+    assert fused._MADE.learn == made and fused._MADE.n == 27
+    assert fused._GLOW.learn == (0, 1, 3, 4, 8, 9, 10) + tuple(11 + i for i in mlp)
+    assert fused._REALNVP.learn == (6, 7) + tuple(8 + i for i in mlp)
+    assert fused._MAF.learn == tuple(9 + i for i in made) + tuple(36 + i for i in made) + (7, 8)
+    cases, ar = _first_step_cases(pkg, fused)
+    for layout, tensors, n, n_learn in cases:
+        assert len(tensors) == n == layout.n
+        learn = fused._learnables(layout, tensors)
+        assert len(learn) == n_learn
+        want = [t for t in tensors if t is not None and t.requires_grad]
+        if layout is fused._MAF:
+            assert {id(t) for t in learn} == {id(t) for t in want} and len(want) == n_learn
+            nets = [fused._learnables(fused._MADE, fused._made_tensors(net)) for net in (ar.net_s, ar.net_t)]
+            want = nets[0] + nets[1] + [ar.s_log_scale, ar.s_bias]
+        assert len(want) == n_learn and all(a is b for a, b in zip(learn, want))
+        # the C ABI takes the step's own gradients and the nets' gradient table apart
+        own, net = learn[layout.ghead], learn[layout.gnet]
+        assert len(own) + len(net) == n_learn
+        assert all(any(t is h for h in tensors[:layout.head]) for t in own)
+        assert all(any(t is m for m in tensors[layout.head:]) for t in net)
+
+
+def test_place_grads_is_the_inverse_of_learnables(pkg):
+    """sentinel k lands in the slot of learnable k, every buffer's slot is None: bare MLP list and the three step families"""
+    import importlib
+    fused = importlib.import_module(pkg.__name__ + '.fused')
+    for layout in (fused._MLP, fused._GLOW, fused._REALNVP, fused._MAF):
+        sentinels = [object() for _ in layout.learn]
+        out = fused._place_grads(layout, sentinels)
+        assert isinstance(out, tuple) and len(out) == layout.n
+        for k, i in enumerate(layout.learn):
+            assert out[i] is sentinels[k]
+        assert all(out[i] is None for i in range(layout.n) if i not in layout.learn)
+        assert fused._learnables(layout, out) == sentinels
+
+
+@pytest.mark.parametrize('scratch', ['_glow_steps_scratch', '_maf_steps_scratch'])
+def test_deferred_fold_scratch_grows_and_retires_only_once_a_capture_has_seen_it(pkg, monkeypatch, scratch):
+    """the (slabs, rec) pairs of the deferred folds: a larger request returns a larger pair; the outgrown pair is dropped while no
+    hipGraph capture has ever asked for scratch and kept alive (a replay may still write to it) once one has"""
+    import importlib
+    fused = importlib.import_module(pkg.__name__ + '.fused')
+    monkeypatch.setattr(fused, '_SCRATCH', {})
+    monkeypatch.setattr(fused, '_GRAPH_SEEN', [False])
+    monkeypatch.setattr(fused, '_capturing', lambda: False)
+    dev = torch.device('cpu')
+    get = getattr(fused, scratch)
+    first = get(2, 1, dev)
+    assert get(2, 1, dev) is first and get(1, 1, dev) is first
+    second = get(2, 2, dev)
+    assert second is not first and second[0].numel() >= 2 * first[0].numel() and second[1].numel() >= 2 * first[1].numel()
+    assert fused._SCRATCH.get(('retired', dev)) is None, 'nothing captured can hold the first pair: it is dropped'
+    monkeypatch.setattr(fused, '_capturing', lambda: True)
+    assert get(2, 2, dev) is second                              # a capture asks: from now on outgrown pairs are kept
+    monkeypatch.setattr(fused, '_capturing', lambda: False)
+    third = get(4, 2, dev)
+    assert third is not second and third[0].numel() > second[0].numel()
+    assert fused._SCRATCH[('retired', dev)] == [second]
+    fourth = get(4, 4, dev)
+    assert [id(t) for t in fused._SCRATCH[('retired', dev)]] == [id(second), id(third)] and fourth[0].numel() > third[0].numel()
+
+
 def test_zero_arena_retires_only_buffers_a_graph_was_captured_against(pkg):
     import importlib
     import torch

@@ -36,10 +36,10 @@ def main():
         a, c = pkg.ActNorm((D, )).to(dev), pkg.InvertibleConv1x1(D).to(dev)
         h = [a.log_scale, a.bias, c.P, c.L, c.U, c.L_mask, c.U_mask, c.sign_s, c.log_s, k.s_log_scale, k.s_bias]
         m = F._mlp_tensors(k.net)
-        steps.append((int(i & 1), h, m))
-        sinks.append([torch.zeros_like(t) for t in F._glow_step_learnables(h, m)])
+        steps.append(h + m)
+        sinks.append([torch.zeros_like(t) for t in F._learnables(F._GLOW, h + m)])
         keep.append((k, a, c))
-    table = F._glow_flow_table(steps, sinks, D, dev)
+    table = F._flow_table(F._GLOW_RUN, tuple((i & 1, ) for i in range(S)), steps, sinks, D, dev)
     host = ctypes.addressof(F._GLOW_FLOW_HOST[table.data_ptr()])
     z, gy = torch.randn(B, D, device=dev), torch.randn(B, D, device=dev)
     ld = torch.zeros(B, device=dev)
@@ -68,7 +68,7 @@ def main():
     nws = N.header_constant('NF_MAF_WS_FLOATS')
     N.call('nf_maf_step_fwd', z.data_ptr(), y.data_ptr(), ld.data_ptr(), ctypes.addressof(htab), ctypes.addressof(mtab),
            save.data_ptr(), torch.zeros(nws, device=dev).data_ptr(), B, D, 1.0e-5, 0.1, 1.0e-5, N.stream())
-    dst = [torch.zeros_like(t) for t in F._made_learnables(made[:27]) + F._made_learnables(made[27:])]
+    dst = [torch.zeros_like(t) for t in F._learnables(F._MADE, made[:27]) + F._learnables(F._MADE, made[27:])]
     gtab = F._ptr_table(dst)
     ga, gc = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
     blocks = (B + 127) // 128

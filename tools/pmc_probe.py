@@ -107,7 +107,7 @@ def main():
         nws = N.header_constant('NF_MAF_WS_FLOATS')
         N.call('nf_maf_step_fwd', z.data_ptr(), y.data_ptr(), ld.data_ptr(), ctypes.addressof(htab), ctypes.addressof(mtab),
                save.data_ptr(), torch.zeros(nws, device=dev).data_ptr(), Nr, D, 1.0e-5, 0.1, 1.0e-5, N.stream())
-        learn = F._made_learnables(made[:27]) + F._made_learnables(made[27:])
+        learn = F._learnables(F._MADE, made[:27]) + F._learnables(F._MADE, made[27:])
         dst = [torch.zeros_like(t) for t in learn]
         gtab = F._ptr_table(dst)
         ga, gc = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
