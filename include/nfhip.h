@@ -859,6 +859,25 @@ int nf_maf_step_fwd(const float* z, float* y, float* ld, const void* const* head
  * ws_zero: D x NF_MAF_WS_FLOATS zero floats (one exchange workspace per pass).  Unlike the reference the input is not mutated. */
 int nf_maf_step_inv(const float* y, float* z, float* ld, const void* const* head, const void* const* made_params, float* ws_zero,
                     int64_t N, int D, int training, float bn_eps, nf_stream_t stream);
+/* nf_maf_step_inv with a mask set of its own per pass, as the reference's inverse draws (maf.py:111-113 calls both MADEs, hence
+ * MADE._create_masks, in each of its D passes): pass i stages the weights of both nets again under the masks at
+ * (mask pointer of made_params) + i * mask_stride floats.  With the draws of nf_made_draw_masks in pass-major order (s-net, then
+ * t-net) the stride is 2 * NF_MADE_MASK_STRIDE.  mask_stride = 0 is nf_maf_step_inv.                                         */
+int nf_maf_step_inv_drawn(const float* y, float* z, float* ld, const void* const* head, const void* const* made_params,
+                          int64_t mask_stride, float* ws_zero, int64_t N, int D, int training, float bn_eps, nf_stream_t stream);
+/* The MADE masks of such a step drawn on the device (MADE._create_masks, maf.py:66-85: three hidden layers of 32 units, D <= 4):
+ * n_draws independent mask sets, one wave each.  Hidden degrees m_l[k] uniform on [lo_l, D - 2], lo_l = min(min_k m_{l-1}[k],
+ * D - 2), m_0 = arange(D); draw d lives at masks + d * NF_MADE_MASK_STRIDE floats, its four fp32 masks (O x I, row-major, as the
+ * step kernels read them) at NF_MADE_MASK_OFF_0 .. _3 (sized for D = 4, packed for the D at hand).  degrees: nullable int32
+ * (n_draws, 3, 32).  Philox4x32-10 keyed by seed[0], counter = (seed[1] + d, layer, unit): the same words give the same masks.
+ * advance != 0: seed[1] += n_draws by a one-thread launch behind the draw (stream order; no workgroup of the draw reads the
+ * word after that write).                                                                                                 */
+#define NF_MADE_MASK_OFF_0 0
+#define NF_MADE_MASK_OFF_1 128
+#define NF_MADE_MASK_OFF_2 1152
+#define NF_MADE_MASK_OFF_3 2176
+#define NF_MADE_MASK_STRIDE 2304
+int nf_made_draw_masks(float* masks, int* degrees, int64_t* seed, int n_draws, int D, int advance, nf_stream_t stream);
 int nf_maf_step_bwd(const float* z, const float* g_y, const float* g_ld, float* g_z, const void* const* head,
                     const void* const* made_params, const float* save_stats, void* const* made_grads, float* g_s_log_scale,
                     float* g_s_bias, float* ws_zero, float* slabs, int64_t N, int D, nf_stream_t stream);

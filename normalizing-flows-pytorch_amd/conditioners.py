@@ -228,18 +228,28 @@ def flowpp_conditioner(in_chs, n_out, mid_shape, base_filters, conv):
 
 # ---- MADE ---------------------------------------------------------------------------------------------------------
 
+def made_masks_from_degrees(D, degrees):
+    """the masks MADE._create_masks (flows/maf.py:66-85) builds from GIVEN hidden degrees: ``degrees`` is one integer vector per hidden
+    layer.  Hidden layer l: m_{l-1}[i] <= m_l[k] with m_0 = arange(D) (maf.py:75); output layer: rows r >= m_last[k] + 1 (maf.py:81-84)."""
+    m_prev = np.arange(D)
+    masks = []
+    for m in degrees:
+        m = np.asarray(m).astype(np.int64)
+        masks.append((m_prev[None, :] <= m[:, None]).astype(np.float32))
+        m_prev = m
+    last = np.zeros((D, len(m_prev)), dtype=np.float32)
+    for k in range(len(m_prev)):
+        last[int(m_prev[k]) + 1:, k] = 1.0
+    masks.append(last)
+    return masks
+
+
 def made_degrees_to_masks(D, num_hidden, base_filters, rng):
     """mask rule of MADE._create_masks (flows/maf.py:66-85), drawing hidden degrees from ``rng.randint``."""
     m_prev = np.arange(D)
-    widths = [D] + [base_filters] * num_hidden
-    masks = []
-    for out_dims in widths[1:]:
+    degrees = []
+    for out_dims in [base_filters] * num_hidden:
         lo = min(int(m_prev.min()), D - 2)
-        m = rng.randint(lo, D - 1, size=(out_dims))
-        masks.append((m_prev[None, :] <= m[:, None]).astype(np.float32))
-        m_prev = m
-    last = np.zeros((D, widths[-1]), dtype=np.float32)
-    for k in range(widths[-1]):
-        last[m_prev[k] + 1:, k] = 1.0
-    masks.append(last)
-    return masks
+        m_prev = rng.randint(lo, D - 1, size=(out_dims))
+        degrees.append(m_prev)
+    return made_masks_from_degrees(D, degrees)

@@ -380,6 +380,32 @@ __device__ __forceinline__ void nf_md_stage(const NfMadeP& p, float* sm, int D) 
     if (tid < 2 * NF_MD_NL * 32) sm[NF_MD_B + tid] = bk;
     if (tid < 2 * NF_MD_NB * 32) { sm[NF_MD_GA + tid] = ga; sm[NF_MD_BE + tid] = be; }
 }
+// the masked weights alone, again, under the masks moff floats behind p.m (the drawn inverse: a mask set per pass; biases and BatchNorm
+// affines stay).  One net at a time: 8 (weight, mask) pairs in flight -- the inverse's row state is live across this.
+__device__ __forceinline__ void nf_md_restage_weights(const NfMadeP& p, float* sm, int D, int64_t moff) {
+    const int tid = threadIdx.x, k = tid & 31;
+#pragma unroll 1
+    for (int n = 0; n < 2; ++n) {
+        float w[NF_MD_NL][2];
+#pragma unroll
+        for (int l = 0; l < NF_MD_NL; ++l) {
+            const int I = l == 0 ? D : 32, O = l == NF_MD_NL - 1 ? D : 32;
+#pragma unroll
+            for (int h2 = 0; h2 < 2; ++h2) {
+                const int oo = (tid >> 5) + 16 * h2;
+                const bool ok = oo < O && k < I;
+                const int e = ok ? oo * I + k : 0;
+                const float wv = p.w[n][l][e], mv = p.m[n][l][moff + e];
+                w[l][h2] = ok ? wv * mv : 0.f;
+            }
+        }
+#pragma unroll
+        for (int l = 0; l < NF_MD_NL; ++l)
+#pragma unroll
+            for (int h2 = 0; h2 < 2; ++h2)
+                sm[NF_MD_W + (n * NF_MD_NL + l) * 32 * NF_FP_ST + ((tid >> 5) + 16 * h2) * NF_FP_ST + k] = w[l][h2];
+    }
+}
 
 __device__ __forceinline__ void nf_md_linear(const float* sm, int n, int l, const float (&av)[8], float (&dv)[8], int c16, int g) {
     f32x4 acc[2] = {nf_fp_zero4(), nf_fp_zero4()};
@@ -455,10 +481,13 @@ __device__ __forceinline__ void nf_md_load_row(const float* z, int64_t row, bool
 // grid exchange, no buffer touched).  MODE 2: the INVERSE step (maf.py:108-119, modules.py:309-322): h.z is the step's output,
 // D sequential passes of the MADE pair each fix one feature, then perm^-1 and the flow BatchNorm's inverse (batch buffers when
 // `training`, running statistics otherwise); with `training` the MADE BatchNorms use batch statistics and update their running
-// statistics once per pass, exactly as D module calls do (pass i exchanges through ws + i * NF_MAF_WS_FLOATS).
-template <int MODE>
+// statistics once per pass, exactly as D module calls do (pass i exchanges through ws + i * NF_MAF_WS_FLOATS).  MODE 3: MODE 2 with a
+// mask set per pass, as the reference's inverse redraws them (maf.py:111-113): pass i > 0 stages the masked weights of both nets
+// again under the masks at p.m + i * mstride floats.  Only that arm reads mstride.
+template <int MODE_>
 __global__ void __launch_bounds__(NF_MD_THREADS) k_maf_step_fwd(NfMadeP p, NfMafV h, float* save, float* ws, int64_t N, float eps,
-                                                                int training) {
+                                                                int training, int64_t mstride) {
+    constexpr int MODE = MODE_ == 3 ? 2 : MODE_;          // the drawn inverse IS the inverse, but for the restaging between passes
     const bool use_batch = MODE == 0 || (MODE == 2 && training != 0);
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, c16 = lane & 15, g = lane >> 4;
@@ -541,7 +570,11 @@ __global__ void __launch_bounds__(NF_MD_THREADS) k_maf_step_fwd(NfMadeP p, NfMaf
     for (int pass = 0; pass < passes; ++pass) {
     if (MODE == 2 && pass > 0) {
         slots += NF_MAF_WS_FLOATS / 2;                    // a fresh exchange workspace per pass
-        __syncthreads();                                  // the previous pass is done with the BatchNorm constants in LDS
+        __syncthreads();                                  // the previous pass is done with the BatchNorm constants and the weights in LDS
+        if (MODE_ == 3) {                                 // this pass's own mask set, behind the barrier above: nobody reads the old weights
+            nf_md_restage_weights(p, sm, D, (int64_t)pass * mstride);
+            __syncthreads();
+        }
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) xa[j] = 0.f;
@@ -967,17 +1000,18 @@ extern "C" int nf_maf_step_fwd(const float* z, float* y, float* ld, const void* 
     }
     if (flow_bn_momentum == NF_FBN_RUNNING)             // evaluation mode: running statistics everywhere, nothing updated
         hipLaunchKernelGGL(k_maf_step_fwd<1>, dim3(grid), dim3(NF_MD_THREADS), lds, (hipStream_t)stream, p, h, save_stats, ws_zero, N,
-                           bn_eps, 0);
+                           bn_eps, 0, (int64_t)0);
     else
         hipLaunchKernelGGL(k_maf_step_fwd<0>, dim3(grid), dim3(NF_MD_THREADS), lds, (hipStream_t)stream, p, h, save_stats, ws_zero, N,
-                           bn_eps, 1);
+                           bn_eps, 1, (int64_t)0);
     NF_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int nf_maf_step_inv(const float* y, float* z, float* ld, const void* const* head, const void* const* made_params,
-                               float* ws_zero, int64_t N, int D, int training, float bn_eps, nf_stream_t stream) {
-    if (y == nullptr || z == nullptr || ld == nullptr || head == nullptr || made_params == nullptr || ws_zero == nullptr ||
+extern "C" int nf_maf_step_inv_drawn(const float* y, float* z, float* ld, const void* const* head, const void* const* made_params,
+                                     int64_t mask_stride, float* ws_zero, int64_t N, int D, int training, float bn_eps,
+                                     nf_stream_t stream) {
+    if (mask_stride < 0 || y == nullptr || z == nullptr || ld == nullptr || head == nullptr || made_params == nullptr || ws_zero == nullptr ||
         !nf_maf_ok(N, D))
         return NF_E_BADARG;
     if (N <= 0) return N == 0 ? 0 : NF_E_BADARG;
@@ -992,12 +1026,23 @@ extern "C" int nf_maf_step_inv(const float* y, float* z, float* ld, const void* 
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute((const void*)k_maf_step_fwd<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
+        e = hipFuncSetAttribute((const void*)k_maf_step_fwd<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
-    hipLaunchKernelGGL(k_maf_step_fwd<2>, dim3(grid), dim3(NF_MD_THREADS), lds, (hipStream_t)stream, p, h, (float*)nullptr, ws_zero, N,
-                       bn_eps, training ? 1 : 0);
+    if (mask_stride != 0)
+        hipLaunchKernelGGL(k_maf_step_fwd<3>, dim3(grid), dim3(NF_MD_THREADS), lds, (hipStream_t)stream, p, h, (float*)nullptr, ws_zero,
+                           N, bn_eps, training ? 1 : 0, mask_stride);
+    else
+        hipLaunchKernelGGL(k_maf_step_fwd<2>, dim3(grid), dim3(NF_MD_THREADS), lds, (hipStream_t)stream, p, h, (float*)nullptr, ws_zero,
+                           N, bn_eps, training ? 1 : 0, (int64_t)0);
     NF_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int nf_maf_step_inv(const float* y, float* z, float* ld, const void* const* head, const void* const* made_params,
+                               float* ws_zero, int64_t N, int D, int training, float bn_eps, nf_stream_t stream) {
+    return nf_maf_step_inv_drawn(y, z, ld, head, made_params, 0, ws_zero, N, D, training, bn_eps, stream);
 }
 
 static int nf_maf_launch_bwd(const float* z, const float* g_y, const float* g_ld, float* g_z, const void* const* head,

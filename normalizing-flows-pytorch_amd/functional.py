@@ -1207,6 +1207,26 @@ def resflow_draws(seed, L, B, D, S, n_exact, fixed_n=0, slots=2, layer0=0):
     return n_terms, noise
 
 
+def made_mask_views(buf, D):
+    """per draw of a (n_draws, NF_MADE_MASK_STRIDE) buffer of nf_made_draw_masks: the four masks [(32, D), (32, 32), (32, 32), (D, 32)] as
+    contiguous views"""
+    offs = [N.header_constant('NF_MADE_MASK_OFF_%d' % l) for l in range(4)]
+    shapes = [(32, D), (32, 32), (32, 32), (D, 32)]
+    return [[buf[d, o:o + r * c].view(r, c) for o, (r, c) in zip(offs, shapes)] for d in range(buf.shape[0])]
+
+
+def made_draw_masks(seed, n_draws, D, want_degrees=False, advance=False):
+    """the MADE masks (flows/maf.py:66-85; three hidden layers of 32, D <= 4) the device draws for the seed words ``seed`` (device
+    int64[2]: seed, stream offset) as they stand now: a list of ``n_draws`` mask sets [(32, D), (32, 32), (32, 32), (D, 32)], views of ONE
+    tensor allocated for this call -- and, with ``want_degrees``, the int32 (n_draws, 3, 32) hidden degrees behind them.  ``advance``
+    moves the stream offset on by n_draws on the device, behind the draw (what the model's own call sites do)."""
+    buf = torch.empty((n_draws, N.header_constant('NF_MADE_MASK_STRIDE')), dtype=torch.float32, device=seed.device)
+    deg = torch.empty((n_draws, 3, 32), dtype=torch.int32, device=seed.device) if want_degrees else None
+    N.call('nf_made_draw_masks', N.ptr(buf), N.ptr(deg), N.ptr(seed, (torch.int64, )), n_draws, D, int(bool(advance)), N.stream())
+    sets = made_mask_views(buf, D)
+    return (sets, deg) if want_degrees else sets
+
+
 class _ResFlowStack(torch.autograd.Function):
     """training forward of <= RESFLOW_MAX_LAYERS blocks (spectral launch + one stack launch) and its backward (one stack launch + the
     fold / spectral-norm autograd launch, gradients added to the parameters' sinks where a GradBucket offers them)"""

@@ -17,6 +17,7 @@ import os as _os
 import torch
 
 from . import _native as N
+from . import functional as NF
 from . import workspace as WS
 from .functional import PluHolder, _owned_ld, _sinks, flush_head_params, grad_sink
 
@@ -1121,8 +1122,7 @@ def maf_step_eval(z, ld, bn, ar):
     """[flow BatchNorm, AutoregressiveTransfrom] in evaluation mode under no_grad: one launch, no grid exchange"""
     z = z.contiguous()
     Nrows, D = z.shape
-    ms = ar.net_s.draw_masks(z.device)                       # same RNG order as the reference: s-net, then t-net
-    mt = ar.net_t.draw_masks(z.device)
+    ms, mt = ar.draw_pair(z.device)                          # same RNG order as the reference: s-net, then t-net
     htab, mtab = _maf_tables(bn, ar, ms, mt)
     ld = _owned_ld(ld)
     y = torch.empty_like(z)
@@ -1137,6 +1137,32 @@ def maf_step_inverse_usable(y, bn, ar):
     """D <= 2: the MADE masks of such nets do not depend on the draw, so the D passes of the reference's inverse (which draws
     anew in every pass) share one set"""
     return GLOW_INVERSE and _maf_struct_ok(y, bn, ar) and y.shape[1] <= 2 and (y.shape[0] > 1 or not bn.training)
+
+
+def maf_step_inverse_drawn_usable(y, bn, ar):
+    """draws = 'device', any D <= 4: the kernel stages the weights again per pass under that pass's own mask set"""
+    return (GLOW_INVERSE and ar.net_s.draws == 'device' and ar.net_t.draws == 'device' and ar.net_s._seed is ar.net_t._seed
+            and _maf_struct_ok(y, bn, ar) and (y.shape[0] > 1 or not bn.training))
+
+
+def maf_step_inverse_drawn(y, ld, bn, ar):
+    """the inverse of [flow BatchNorm, AutoregressiveTransfrom] in one launch with the masks drawn on the device: the reference draws
+    both nets' masks anew in each of its D passes (maf.py:111-113), so the launch reads 2 D draws, pass-major, s-net before t-net"""
+    from .layers import made_seed_words
+    with torch.no_grad():
+        y = y.contiguous()
+        Nrows, D = y.shape
+        drawn = NF.made_draw_masks(made_seed_words(ar.net_s, y.device), 2 * D, D, advance=True)
+        ar.net_s.masks, ar.net_t.masks = drawn[2 * D - 2], drawn[2 * D - 1]
+        htab, mtab = _maf_tables(bn, ar, drawn[0], drawn[1])
+        training = bool(bn.training)
+        nws = D * N.header_constant('NF_MAF_WS_FLOATS')
+        ws = WS.zeros(nws, y.device) if training else torch.empty(nws, dtype=torch.float32, device=y.device)
+        ld = ld.clone()
+        z = torch.empty_like(y)
+        N.call('nf_maf_step_inv_drawn', N.ptr(y), N.ptr(z), N.ptr(ld), ctypes.addressof(htab), ctypes.addressof(mtab),
+               2 * N.header_constant('NF_MADE_MASK_STRIDE'), N.ptr(ws), Nrows, D, int(training), BN_EPS, N.stream())
+        return z, ld
 
 
 def maf_step_inverse(y, ld, bn, ar):
@@ -1416,8 +1442,7 @@ class _MAFStepVec(torch.autograd.Function):
 
 def maf_step_vec(z, ld, bn, ar):
     """[flow BatchNorm ``bn`` (training, affine=False), AutoregressiveTransfrom ``ar``] on (N, D) data, fused."""
-    ms = ar.net_s.draw_masks(z.device)                       # same RNG order as the reference: s-net, then t-net
-    mt = ar.net_t.draw_masks(z.device)
+    ms, mt = ar.draw_pair(z.device)                          # same RNG order as the reference: s-net, then t-net
     return _MAFStepVec.apply(z, _owned_ld(ld), bn.eps, bn.momentum, *_maf_step_tensors(bn, ar, ms, mt))
 
 
@@ -1510,9 +1535,17 @@ def maf_flow_vec_usable(z, steps):
 
 def maf_flow_vec(z, ld, steps):
     tensors, metas = [], []
-    for bn, ar in steps:
-        ms = ar.net_s.draw_masks(z.device)                   # same RNG order as the reference: per step s-net, then t-net
-        mt = ar.net_t.draw_masks(z.device)
+    nets = [n for _, ar in steps for n in (ar.net_s, ar.net_t)]
+    drawn = None
+    if all(n.draws == 'device' and n._seed is nets[0]._seed for n in nets):
+        from .layers import made_seed_words
+        # the 2 S draws of the run in ONE launch, step-major with the s-net before the t-net (the reference's call order)
+        drawn = NF.made_draw_masks(made_seed_words(nets[0], z.device), len(nets), z.shape[1], advance=True)
+    for i, (bn, ar) in enumerate(steps):
+        if drawn is not None:
+            ms, mt = ar.net_s.masks, ar.net_t.masks = drawn[2 * i], drawn[2 * i + 1]
+        else:
+            ms, mt = ar.draw_pair(z.device)                  # same RNG order as the reference: per step s-net, then t-net
         tensors += _maf_step_tensors(bn, ar, ms, mt)
         metas.append((float(bn.eps), float(bn.momentum)))
     return _MAFFlowVec.apply(z, _owned_ld(ld), tuple(metas), *tensors)

@@ -375,6 +375,11 @@ class Compose(nn.Module):
                 i -= 2 * len(run)
                 continue
             if self._maf_pair_at(i - 1, z) and not (torch.is_grad_enabled() and z.requires_grad) \
+                    and FUSED.maf_step_inverse_drawn_usable(z, self.layers[i - 1], self.layers[i]):
+                z, log_df_dz = FUSED.maf_step_inverse_drawn(z, log_df_dz, self.layers[i - 1], self.layers[i])    # device draws: a mask set per pass
+                i -= 2
+                continue
+            if self._maf_pair_at(i - 1, z) and not (torch.is_grad_enabled() and z.requires_grad) \
                     and FUSED.maf_step_inverse_usable(z, self.layers[i - 1], self.layers[i]):
                 z, log_df_dz = FUSED.maf_step_inverse(z, log_df_dz, self.layers[i - 1], self.layers[i])
                 i -= 2
@@ -1010,7 +1015,11 @@ class MixLogAttnCoupling(AbstractCoupling):
 class MADE(nn.Module):
     """masked autoencoder conditioner, flows/maf.py:9-85.  Same parameter containers (weights / bnorms / biases).
     Masks follow the reference's rule, including its re-draw from the global ``np.random`` on every call
-    (degenerate, i.e. constant, for D == 2 -- appendix D Q4)."""
+    (degenerate, i.e. constant, for D == 2 -- appendix D Q4).  ``draws = 'device'`` (set through ``MAF.draws``) takes every draw from
+    csrc/made_masks.hip instead: same rule, Philox in place of np.random, nothing from the host."""
+
+    draws = 'host'                  # (MAF.draws: where the masks are drawn)
+    _seed = None                    # (MAF.seed: device int64[2], the seed words of draws = 'device')
 
     def __init__(self, in_out_features, num_hidden=2, base_filters=32, use_companion=False):
         super().__init__()
@@ -1020,8 +1029,8 @@ class MADE(nn.Module):
         self.num_hidden = num_hidden
         self.base_filters = base_filters
         self.masks = None
-        # the draw changes from call to call for D > 2 (constant for D == 2): a captured graph would freeze it -- FlowTrainer then
-        # keeps such a model on eager launches (train.py)
+        # the draw changes from call to call for D > 2 (constant for D == 2): a captured graph would freeze a host draw -- FlowTrainer
+        # then switches a MAF on the GPU to device draws and keeps any other such model on eager launches (train.py)
         self.masks_redrawn_per_call = in_out_features > 2
         weights, biases, bnorms = [], [], []
         widths = [in_out_features] + [base_filters] * num_hidden
@@ -1041,7 +1050,11 @@ class MADE(nn.Module):
 
     def draw_masks(self, device):
         """draws the masks like the reference does on every call; the device copies are re-used while the draw is
-        unchanged (always, for D == 2), so the steady state has no host-to-device traffic."""
+        unchanged (always, for D == 2), so the steady state has no host-to-device traffic.  draws = 'device': one launch, one draw,
+        into a tensor of its own."""
+        if self.draws == 'device':
+            self.masks = NF.made_draw_masks(made_seed_words(self, device), 1, self.in_out_chs, advance=True)[0]
+            return self.masks
         m = made_degrees_to_masks(self.in_out_chs, self.num_hidden, self.base_filters, np.random)
         c = getattr(self, '_mask_cache', None)
         if c is None or c[0] != device or not all(np.array_equal(a, b) for a, b in zip(c[1], m)):
@@ -1060,6 +1073,16 @@ class MADE(nn.Module):
         return F.linear(h, self.weights[-1] * masks[-1], self.biases[-1])
 
 
+def made_seed_words(net, device):
+    """the seed words a MADE in draws = 'device' mode draws from"""
+    if net.num_hidden != 3 or net.base_filters != 32:
+        raise RuntimeError("draws='device' serves MADEs of three hidden layers of 32 units (csrc/made_masks.hip)")
+    if net._seed is None or net._seed.device != device or not net._seed.is_cuda:
+        raise RuntimeError("draws='device' needs the model's seed words on the input's GPU (set it through MAF.draws and call the MAF "
+                           "model; got seed on %s, input on %s)" % (None if net._seed is None else net._seed.device, device))
+    return net._seed
+
+
 class AutoregressiveTransfrom(nn.Module):
     """masked autoregressive affine transform (the reference's spelling), flows/maf.py:88-119."""
 
@@ -1072,14 +1095,23 @@ class AutoregressiveTransfrom(nn.Module):
         self.s_log_scale = nn.Parameter(torch.randn(1) * 0.01)
         self.s_bias = nn.Parameter(torch.randn(1) * 0.01)
 
+    def draw_pair(self, device):
+        """(masks of net s, masks of net t) of one call, in the reference's RNG order: s-net, then t-net; draws = 'device': both from
+        one launch"""
+        if self.net_s.draws == 'device' and self.net_t.draws == 'device' and self.net_s._seed is self.net_t._seed:
+            self.net_s.masks, self.net_t.masks = NF.made_draw_masks(made_seed_words(self.net_s, device), 2, self.in_out_chs, advance=True)
+        else:
+            self.net_s.draw_masks(device)
+            self.net_t.draw_masks(device)
+        return self.net_s.masks, self.net_t.masks
+
     def conditioners(self, z):
         """(s_raw, t) = (net_s(z), net_t(z)); on the GPU both MADEs run in the same fp32-MFMA launches."""
         from . import dist as nfdist
         if (z.is_cuda and self.in_out_chs <= 32 and self.net_s.base_filters == 32 and z.dtype == torch.float32
                 and not nfdist.sync_stats_active()):
             from .fused import made_pair_forward
-            ms = self.net_s.draw_masks(z.device)             # same RNG order as the reference: s-net, then t-net
-            mt = self.net_t.draw_masks(z.device)
+            ms, mt = self.draw_pair(z.device)
             return made_pair_forward(self.net_s, self.net_t, z, ms, mt)
         return self.net_s(z), self.net_t(z)
 

@@ -189,6 +189,43 @@ class MAF(_FlowModel):
             layers.append(AutoregressiveTransfrom(dims[0]))
         return layers
 
+    def __init__(self, dims, datatype=None, cfg=None):
+        super().__init__(dims, datatype, cfg)
+        # seed words of the device-side mask draws (draws = 'device'): seed, stream offset; not in the state_dict
+        self.register_buffer('seed', torch.tensor([torch.initial_seed() & 0x7fffffffffffffff, 0], dtype=torch.int64), persistent=False)
+
+    def _mades(self):
+        return [n for m in self.net.layers if isinstance(m, AutoregressiveTransfrom) for n in (m.net_s, m.net_t)]
+
+    @property
+    def draws(self):
+        """'host' (default): the MADE masks are redrawn from np.random on every call, in the reference's order (maf.py:50,66-85);
+        'device': drawn by csrc/made_masks.hip from ``seed`` with the same rule (what a captured training step needs for D > 2: a
+        replay draws afresh; and what lets the inverse of a step with D > 2 run as one launch).  D <= 4."""
+        return self._mades()[0].draws if self.n_layers > 0 else 'host'
+
+    @draws.setter
+    def draws(self, value):
+        if value not in ('host', 'device'):
+            raise ValueError("draws is 'host' or 'device', got %r" % (value, ))
+        if value == 'device' and self.dims[0] > 4:
+            raise ValueError("draws = 'device' serves D <= 4 (csrc/made_masks.hip), got D = %d" % self.dims[0])
+        for n in self._mades():
+            n.draws = value
+        self._bind_seed()
+
+    def _bind_seed(self):
+        for n in self._mades():                              # (every pass: .to() replaces the buffer)
+            n._seed = self.seed
+
+    def forward(self, z):
+        self._bind_seed()
+        return super().forward(z)
+
+    def backward(self, z):
+        self._bind_seed()
+        return super().backward(z)
+
 
 class PlanarFlow(nn.Module):
     """flows/planar.py:71-94: ``cfg.layers`` PlanarTransforms on the flattened dimension.  The reference also builds a BatchNorm per

@@ -300,12 +300,17 @@ class FlowTrainer:
         self.sync_stats = bool(sync_stats)
         if self.sync_stats:
             graph = False
-        if graph and any(getattr(m_, 'masks_redrawn_per_call', False) for m_ in net.modules()):
-            # MADE re-draws its masks from the host's np.random on every call (flows/maf.py:50,72); for D > 2 the draw varies, and a
-            # replayed graph would repeat the masks of the captured step: such models train on eager launches
-            graph = False
         self.sampler = sampler      # data.DeviceSampler: train_on_batch() without a batch draws one on the device, inside the graph
         on_gpu = next(net.parameters()).is_cuda
+        if graph and any(getattr(m_, 'masks_redrawn_per_call', False) and getattr(m_, 'draws', 'host') != 'device' for m_ in net.modules()):
+            # MADE re-draws its masks from the host's np.random on every call (flows/maf.py:50,72); for D > 2 the draw varies, and a
+            # replayed graph would repeat the masks of the captured step.  A MAF on the GPU draws them on the device instead
+            # (MAF.draws = 'device', D <= 4); any other such model trains on eager launches
+            from .models import MAF
+            if on_gpu and isinstance(net, MAF) and net.dims[0] <= 4:
+                net.draws = 'device'
+            else:
+                graph = False
         if graph and on_gpu:
             # a Residual Flow draws its series lengths and noise from the host generators by default: a captured step would replay one
             # frozen draw (or fail at capture on the host-to-device copies).  Its whole-stack kernels draw on the device instead.
