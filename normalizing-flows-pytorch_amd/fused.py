@@ -1133,55 +1133,53 @@ def maf_step_eval(z, ld, bn, ar):
     return y, ld
 
 
+def maf_device_draws(ar):
+    return ar.net_s.draws == 'device' and ar.net_t.draws == 'device' and ar.net_s._seed is ar.net_t._seed
+
+
 def maf_step_inverse_usable(y, bn, ar):
-    """D <= 2: the MADE masks of such nets do not depend on the draw, so the D passes of the reference's inverse (which draws
-    anew in every pass) share one set"""
-    return GLOW_INVERSE and _maf_struct_ok(y, bn, ar) and y.shape[1] <= 2 and (y.shape[0] > 1 or not bn.training)
+    """draws = 'device': any D <= 4, the kernel stages the weights again per pass under that pass's own mask set.  Host draws: D <= 2,
+    where the MADE masks do not depend on the draw, so the D passes of the reference's inverse (which draws anew in every pass) share
+    one set"""
+    return (GLOW_INVERSE and _maf_struct_ok(y, bn, ar) and (y.shape[0] > 1 or not bn.training)
+            and (maf_device_draws(ar) or y.shape[1] <= 2))
 
 
-def maf_step_inverse_drawn_usable(y, bn, ar):
-    """draws = 'device', any D <= 4: the kernel stages the weights again per pass under that pass's own mask set"""
-    return (GLOW_INVERSE and ar.net_s.draws == 'device' and ar.net_t.draws == 'device' and ar.net_s._seed is ar.net_t._seed
-            and _maf_struct_ok(y, bn, ar) and (y.shape[0] > 1 or not bn.training))
-
-
-def maf_step_inverse_drawn(y, ld, bn, ar):
-    """the inverse of [flow BatchNorm, AutoregressiveTransfrom] in one launch with the masks drawn on the device: the reference draws
-    both nets' masks anew in each of its D passes (maf.py:111-113), so the launch reads 2 D draws, pass-major, s-net before t-net"""
-    from .layers import made_seed_words
+def _maf_step_inverse(y, ld, bn, ar, device_draws):
+    """the inverse of [flow BatchNorm, AutoregressiveTransfrom] in one launch (maf.py:108-119, modules.py:309-322).  The reference draws
+    both nets' masks anew in each of its D passes (maf.py:111-113): with device draws the launch reads those 2 D draws, pass-major, s-net
+    before t-net; with host draws it reads the one set they all equal, after the same RNG consumption."""
     with torch.no_grad():
         y = y.contiguous()
         Nrows, D = y.shape
-        drawn = NF.made_draw_masks(made_seed_words(ar.net_s, y.device), 2 * D, D, advance=True)
-        ar.net_s.masks, ar.net_t.masks = drawn[2 * D - 2], drawn[2 * D - 1]
-        htab, mtab = _maf_tables(bn, ar, drawn[0], drawn[1])
-        training = bool(bn.training)
-        nws = D * N.header_constant('NF_MAF_WS_FLOATS')
-        ws = WS.zeros(nws, y.device) if training else torch.empty(nws, dtype=torch.float32, device=y.device)
-        ld = ld.clone()
-        z = torch.empty_like(y)
-        N.call('nf_maf_step_inv_drawn', N.ptr(y), N.ptr(z), N.ptr(ld), ctypes.addressof(htab), ctypes.addressof(mtab),
-               2 * N.header_constant('NF_MADE_MASK_STRIDE'), N.ptr(ws), Nrows, D, int(training), BN_EPS, N.stream())
-        return z, ld
-
-
-def maf_step_inverse(y, ld, bn, ar):
-    """the inverse of [flow BatchNorm, AutoregressiveTransfrom] in one launch (maf.py:108-119, modules.py:309-322)"""
-    with torch.no_grad():
-        y = y.contiguous()
-        Nrows, D = y.shape
-        for _ in range(D):                                   # the reference draws per pass and net: same RNG consumption
-            ms = ar.net_s.draw_masks(y.device)
-            mt = ar.net_t.draw_masks(y.device)
+        if device_draws:
+            from .layers import made_seed_words
+            drawn = NF.made_draw_masks(made_seed_words(ar.net_s, y.device), 2 * D, D, advance=True)
+            ar.net_s.masks, ar.net_t.masks = drawn[2 * D - 2], drawn[2 * D - 1]
+            ms, mt = drawn[0], drawn[1]
+            entry, stride = 'nf_maf_step_inv_drawn', (2 * N.header_constant('NF_MADE_MASK_STRIDE'), )
+        else:
+            for _ in range(D):
+                ms = ar.net_s.draw_masks(y.device)
+                mt = ar.net_t.draw_masks(y.device)
+            entry, stride = 'nf_maf_step_inv', ()
         htab, mtab = _maf_tables(bn, ar, ms, mt)
         training = bool(bn.training)
         nws = D * N.header_constant('NF_MAF_WS_FLOATS')
         ws = WS.zeros(nws, y.device) if training else torch.empty(nws, dtype=torch.float32, device=y.device)
         ld = ld.clone()
         z = torch.empty_like(y)
-        N.call('nf_maf_step_inv', N.ptr(y), N.ptr(z), N.ptr(ld), ctypes.addressof(htab), ctypes.addressof(mtab), N.ptr(ws), Nrows, D,
+        N.call(entry, N.ptr(y), N.ptr(z), N.ptr(ld), ctypes.addressof(htab), ctypes.addressof(mtab), *stride, N.ptr(ws), Nrows, D,
                int(training), BN_EPS, N.stream())
         return z, ld
+
+
+def maf_step_inverse_drawn(y, ld, bn, ar):
+    return _maf_step_inverse(y, ld, bn, ar, True)
+
+
+def maf_step_inverse(y, ld, bn, ar):
+    return _maf_step_inverse(y, ld, bn, ar, False)
 
 
 # ---- RealNVP runs in evaluation mode (density evaluation under no_grad) and their inverse (sampling) ------------------------------

@@ -35,11 +35,34 @@ HEAD_IN_CHAIN = True            # (internal: that head's forward in the prologue
 FLOWPP_HEAD_ON = True           # (internal: image Flow++ steps take the fused Glow heads too; tests compare with the three layers' own launches)
 
 
+def _unhooked(*mods, backward=()):
+    """no forward or pre-forward hook on any of ``mods`` and no backward hook on any of ``backward``: the fused launches run none
+    of them (the reference's debug mode registers NaN hooks, main.py:312-313)"""
+    for m in mods:
+        if m._forward_hooks or m._forward_pre_hooks:
+            return False
+    for m in backward:
+        if m._backward_hooks:
+            return False
+    return True
+
+
+def _vector_coupling(k):
+    """an AffineCoupling over the two halves of a vector whose conditioner is the MLP the fused vector steps carry"""
+    return type(k) is AffineCoupling and k.mode == N.SPLIT_1D and isinstance(k.net, MLP)
+
+
+def _autoregressive(k):
+    return type(k) is AutoregressiveTransfrom
+
+
 class Compose(nn.Module):
-    """flows/modules.py:325-339.  The forward direction applies one peephole fusion: a Glow flow step
-    [ActNorm, InvertibleConv1x1, AffineCoupling] on <= 4 channels runs its first two layers and the coupling's
-    split-gather as ONE launch (functional.glow_head) -- same math, same parameters, same state_dict; skipped when a
-    member carries forward hooks (the reference's debug mode registers NaN hooks, main.py:312-313)."""
+    """flows/modules.py:325-339.  Both directions walk the layers through an ordered list of routes (``_FORWARD``, ``_INVERSE``; DESIGN.md
+    section 4): each route recognises a step shape at the current layer -- a run of planar layers, of ResFlow pairs, of vector Glow,
+    RealNVP or MAF steps, one flow-BatchNorm or Glow step, a Flow++ pair -- and serves it with the fused launches of fused.py /
+    functional.py, or declines; the last route is the layer's own call.  Earlier routes shadow later ones.  Same math, same parameters,
+    same state_dict; every fused route declines when a member carries forward hooks, when ``fuse`` is off and in the
+    synchronised-statistics parity mode."""
 
     fuse = True
     _resflow_draws = 'host'         # (ResFlow.draws: where the whole-stack ResFlow kernels take series lengths and noise from)
@@ -56,109 +79,74 @@ class Compose(nn.Module):
         from . import dist as nfdist
         return self.fuse and not nfdist.sync_stats_active()
 
-    def _glow_step_at(self, i, z):
-        L = self.layers
-        if not (self._fuse_now and z.is_cuda and i + 2 < len(L) and z.shape[1] <= NF.HEAD_MAX_C):
-            return False
-        a, c, k = L[i], L[i + 1], L[i + 2]
-        if not (type(a) is ActNorm and type(c) is InvertibleConv1x1 and (type(k) is AffineCoupling or self._flowpp_image_coupling(k, z))):
-            return False
-        return not (a._forward_hooks or c._forward_hooks or k._forward_hooks or a._forward_pre_hooks
-                    or c._forward_pre_hooks or k._forward_pre_hooks)
-
+    # ---- matchers: one per step shape, the members or None ---------------------------------------------------------------------------
     @staticmethod
     def _flowpp_image_coupling(k, z):
         """an image Flow++ step [ActNorm, InvertibleConv1x1, MixLogAttnCoupling] (flows/flowpp.py:64-70) takes the same fused head as a Glow
         step: ActNorm + 1x1 + the conditioner-input gather in one launch, its backward in two parts (round 5)"""
         return FLOWPP_HEAD_ON and type(k) is MixLogAttnCoupling and z.dim() == 4 and k.mode in (N.SPLIT_CHANNEL, N.SPLIT_CHECKER)
 
-    def _glow_step_w_at(self, i, z):
-        """[ActNorm, InvertibleConv1x1 (weight assembled by the model's batched PLU pre-pass), AffineCoupling] on image data with
-        more channels than the in-kernel PLU head takes"""
+    def _glow_triple_at(self, i, z):
+        """[ActNorm, InvertibleConv1x1, AffineCoupling | image MixLogAttnCoupling] at layers i .. i + 2, whatever the channel count"""
         L = self.layers
-        if not (GLOW_HEAD_W_ON and self._fuse_now and z.is_cuda and z.dim() == 4 and i + 2 < len(L) and z.shape[1] > NF.HEAD_MAX_C):
-            return False
+        if not (self._fuse_now and z.is_cuda and 0 <= i and i + 2 < len(L)):
+            return None
         a, c, k = L[i], L[i + 1], L[i + 2]
         if not (type(a) is ActNorm and type(c) is InvertibleConv1x1 and (type(k) is AffineCoupling or self._flowpp_image_coupling(k, z))):
-            return False
-        if c._W_eff is None or k.mode not in (N.SPLIT_CHANNEL, N.SPLIT_CHECKER) or not NF.glow_head_w_usable(z, k.mode):
-            return False
-        return not (a._forward_hooks or c._forward_hooks or k._forward_hooks or a._forward_pre_hooks
-                    or c._forward_pre_hooks or k._forward_pre_hooks)
-
-    def _glow_run_at(self, i, z):
-        """the maximal run of fused-step-capable Glow steps on (N, 2 | 4) data that starts at layer i -- initialised ActNorms,
-        training-mode conditioners of one mind, every parameter with a direct gradient sink -- or None."""
-        L, run, j = self.layers, [], i
-        if z.dim() != 2:
             return None
-        while self._glow_step_at(j, z):
-            a, c, k = L[j], L[j + 1], L[j + 2]
-            if not (a.initialized and k.mode == N.SPLIT_1D and isinstance(k.net, MLP)
-                    and k.net.training == L[i + 2].net.training):
-                break
-            run.append((a, c, k))
-            j += 3
-        if FUSED.glow_flow_nograd_usable(z, run):            # density evaluation: no autograd node at all
-            return ('nograd', run)
-        return run if FUSED.glow_flow_vec_usable(z, run) else None
+        return (a, c, k) if _unhooked(a, c, k) else None
 
-    def _realnvp_run_at(self, i, z):
-        """the maximal run of fused-step-capable RealNVP steps [flow BatchNorm, AffineCoupling(MLP)] on (N, 2 | 4) data, or None"""
-        L, run, j = self.layers, [], i
-        if z.dim() != 2:
-            return None
-        while self._bn_step_at(j, z):
-            a, k = L[j], L[j + 1]
-            if not (type(k) is AffineCoupling and k.mode == N.SPLIT_1D and isinstance(k.net, MLP)):
-                break
-            run.append((a, k))
-            j += 2
-        return run if FUSED.realnvp_flow_vec_usable(z, run) else None
+    def _glow_vec_step_at(self, i, z):
+        """the Glow triple at i whose coupling is a vector coupling: a member of the fused runs of both directions"""
+        m = self._glow_triple_at(i, z) if z.shape[1] <= NF.HEAD_MAX_C else None
+        return m if m is not None and _vector_coupling(m[2]) else None
 
-    def _maf_run_at(self, i, z):
-        """the maximal run of fused-step-capable MAF steps [flow BatchNorm, AutoregressiveTransfrom] on (N, D <= 4) data, or None"""
-        L, run, j = self.layers, [], i
-        if z.dim() != 2:
-            return None
-        while self._bn_step_at(j, z) and type(L[j + 1]) is AutoregressiveTransfrom:
-            run.append((L[j], L[j + 1]))
-            j += 2
-        return run if FUSED.maf_flow_vec_usable(z, run) else None
-
-    def _bn_step_at(self, i, z):
-        """[flow BatchNorm (training, affine=False), AffineCoupling | AutoregressiveTransfrom] -> fused BatchNorm head"""
+    def _bn_pair_at(self, i, z, training_only, kind=None):
+        """[flow BatchNorm(affine=False), AffineCoupling | AutoregressiveTransfrom] at layers i, i + 1.  ``training_only``: the BatchNorm
+        in training mode on any data (the fused BatchNorm head and the steps built on it); otherwise any mode, vector data (the
+        evaluation and inverse launches).  ``kind``: a narrower test of the second layer (_vector_coupling | _autoregressive)"""
         L = self.layers
-        if not (self._fuse_now and z.is_cuda and i + 1 < len(L)):
-            return False
+        if not (self._fuse_now and z.is_cuda and 0 <= i and i + 1 < len(L) and (training_only or z.dim() == 2)):
+            return None
         a, k = L[i], L[i + 1]
-        if not (type(a) is BatchNorm and a.training and not isinstance(a.log_gamma, nn.Parameter)):
-            return False
-        if not (type(k) is AffineCoupling or type(k) is AutoregressiveTransfrom):
-            return False
-        return not (a._forward_hooks or k._forward_hooks or a._forward_pre_hooks or k._forward_pre_hooks)
+        if not (type(a) is BatchNorm and not isinstance(a.log_gamma, nn.Parameter) and (a.training or not training_only)):
+            return None
+        if not (kind(k) if kind is not None else type(k) is AffineCoupling or type(k) is AutoregressiveTransfrom):
+            return None
+        return (a, k) if _unhooked(a, k) else None
+
+    def _realnvp_any_mode_at(self, i, z):
+        return self._bn_pair_at(i, z, False, _vector_coupling)
 
     def _flowpp_pair_at(self, i, z):
         """[MixLogAttnCoupling, ActNorm (initialised)] on two features -> the next step's ActNorm rides the coupling's launches"""
         L = self.layers
-        if not (self._fuse_now and z.is_cuda and i + 1 < len(L)):
-            return False
+        if not (self._fuse_now and z.is_cuda and 0 <= i and i + 1 < len(L)):
+            return None
         k, a = L[i], L[i + 1]
         if not (type(k) is MixLogAttnCoupling and type(a) is ActNorm and k.mode == N.SPLIT_1D):
-            return False
-        if a._forward_hooks or k._forward_hooks or a._forward_pre_hooks or k._forward_pre_hooks:
-            return False
-        return FUSED.flowpp_post_actnorm_usable(z, k, a)
+            return None
+        return (k, a) if _unhooked(a, k) and FUSED.flowpp_post_actnorm_usable(z, k, a) else None
+
+    # ---- runs ------------------------------------------------------------------------------------------------------------------------
+    def _collect(self, i, z, step, width, member):
+        """the maximal run of steps of ``width`` layers each, in forward order.  step +1: layer i is the first layer of the first step;
+        -1: layer i is the last layer of the last step.  ``member(j, z)`` yields the step that starts at layer j, or None"""
+        run, j, n = [], (i if step > 0 else i - width + 1), len(self.layers)
+        while 0 <= j and j + width <= n:
+            m = member(j, z)
+            if m is None:
+                break
+            run.append(m)
+            j += step * width
+        return run if step > 0 else run[::-1]
 
     def _planar_run(self, i, z, step):
-        """the maximal run of PlanarTransforms without hooks from layer i on (step +1: forward order, -1: backward), on the GPU"""
-        L, run, j = self.layers, [], i
+        """the maximal run of PlanarTransforms without hooks from layer i on, on the GPU"""
+        L = self.layers
         if not z.is_cuda:
-            return run
-        while 0 <= j < len(L) and type(L[j]) is PlanarTransform and not (L[j]._forward_hooks or L[j]._forward_pre_hooks):
-            run.append(L[j])
-            j += step
-        return run
+            return []
+        return self._collect(i, z, step, 1, lambda j, z: L[j] if type(L[j]) is PlanarTransform and _unhooked(L[j]) else None)
 
     def _resflow_run(self, i, z, step):
         """the maximal run of [ActNorm (initialised), InvertibleResLinear] pairs from layer i on (step +1: i is the first pair's ActNorm;
@@ -166,185 +154,200 @@ class Compose(nn.Module):
         hidden width 32, two LipSwish layers, float32 on the GPU), of one mind (mode, estimator, coeff, ftol, noise source), no hooks.
         While an ActNorm awaits its data-dependent initialisation the per-layer path runs."""
         from .resflow import InvertibleResLinear
-        L, run = self.layers, []
+        L, first = self.layers, []
         if not (NF.RESFLOW_STACK and z.is_cuda):
-            return run
-        j = i if step > 0 else i - 1
-        while 0 <= j and j + 1 < len(L):
+            return []
+
+        def mind(k):
+            return (k.training, k.estimator, k.coeff, k.ftol, k.noise_on_cpu, k._sn_eps())
+
+        def member(j, z):
             a, k = L[j], L[j + 1]
             if not (type(a) is ActNorm and type(k) is InvertibleResLinear and a.initialized and k._hip_ok(z)):
-                break
-            if (a._forward_hooks or a._forward_pre_hooks or k._forward_hooks or k._forward_pre_hooks or a._backward_hooks or k._backward_hooks):
-                break
+                return None
+            if not _unhooked(a, k, backward=(a, k)):               # (the one route that looks at both members' backward hooks)
+                return None
             if step > 0 and not ((not k.training and not torch.is_grad_enabled()) or (k.training and torch.is_grad_enabled() and k.hip_training)):
-                break                                              # (the combinations the block itself serves with kernels, resflow.py)
-            if run:
-                f = run[0][1] if step > 0 else run[-1][1]
-                if (k.training, k.estimator, k.coeff, k.ftol, k.noise_on_cpu, k._sn_eps()) != \
-                        (f.training, f.estimator, f.coeff, f.ftol, f.noise_on_cpu, f._sn_eps()):
-                    break
-            run.append((a, k))
-            j += 2 * step
-        return run if step > 0 else run[::-1]
+                return None                                        # (the combinations the block itself serves with kernels, resflow.py)
+            if first and mind(k) != mind(first[0]):                # of one mind with the first member collected
+                return None
+            first.append(k)
+            return a, k
+        return self._collect(i, z, step, 2, member)
+
+    # ---- forward routes: (i, z, ld) -> (z, ld, layers consumed), or None where the route does not serve layer i ------------------------
+    def _planar(self, i, z, ld):
+        run = self._planar_run(i, z, 1) if self._fuse_now else []
+        if run:                                                    # the run of planar layers: projection + one launch
+            return (*NF.planar_flow(z, ld, run), len(run))
+
+    def _resflow(self, i, z, ld):
+        run = self._resflow_run(i, z, 1) if self._fuse_now else []
+        if run:                                                    # the run of residual blocks: a handful of launches whatever its length
+            return (*NF.resflow_flow(z, ld, run, self._resflow_draws, self._resflow_seed), 2 * len(run))
+
+    def _realnvp_eval(self, i, z, ld):
+        run = [] if torch.is_grad_enabled() else self._collect(i, z, 1, 2, self._realnvp_any_mode_at)
+        if run and FUSED.realnvp_eval_usable(z, run):              # density evaluation: the run in one launch, no exchange
+            return (*FUSED.realnvp_flow_vec_eval(z, ld, run), 2 * len(run))
+
+    def _maf_eval(self, i, z, ld):
+        m = self._bn_pair_at(i, z, False, _autoregressive)
+        if m is not None and FUSED.maf_step_eval_usable(z, *m):    # density evaluation: one launch, no exchange
+            return (*FUSED.maf_step_eval(z, ld, *m), 2)
+
+    def _bn_step(self, i, z, ld):
+        """a training-mode flow BatchNorm in front of a coupling or a MADE transform: the run of steps, the whole step, or the fused
+        BatchNorm head in front of the second layer's own launches"""
+        m = self._bn_pair_at(i, z, True)
+        if m is None:
+            return None
+        a, k = m
+        if _vector_coupling(k):
+            run = self._collect(i, z, 1, 2, lambda j, z: self._bn_pair_at(j, z, True, _vector_coupling)) if z.dim() == 2 else []
+            if FUSED.realnvp_flow_vec_usable(z, run):              # the whole run of steps: one launch per direction
+                return (*FUSED.realnvp_flow_vec(z, ld, run), 2 * len(run))
+            if FUSED.realnvp_step_vec_usable(z, a, k.net):
+                return (*FUSED.realnvp_step_vec(z, ld, a, k), 2)                  # the whole step: one launch
+        if type(k) is AffineCoupling:
+            h, z1c, ld = NF.flowbn_head(z, ld, a, k.mode, k.odd, gather=True)
+            return (*k.couple(h, z1c, ld), 2)
+        if FUSED.maf_step_usable(z, a, k):
+            run = self._collect(i, z, 1, 2, lambda j, z: self._bn_pair_at(j, z, True, _autoregressive)) if z.dim() == 2 else []
+            if FUSED.maf_flow_vec_usable(z, run):                  # the run as one autograd node, one fold for all steps
+                return (*FUSED.maf_flow_vec(z, ld, run), 2 * len(run))
+            return (*FUSED.maf_step_vec(z, ld, a, k), 2)                          # the whole step: one launch
+        h, ld = NF.flowbn_head(z, ld, a)
+        return (*k(h, ld), 2)
+
+    def _glow_step(self, i, z, ld):
+        """a Glow flow step on vector data or on up to HEAD_MAX_C channels: the run of steps, the whole step, or the head + the coupling"""
+        m = self._glow_triple_at(i, z) if z.shape[1] <= NF.HEAD_MAX_C else None
+        if m is None:
+            return None
+        a, c, k = m
+        if z.dim() == 2:
+            # (initialised ActNorms, training-mode conditioners of one mind; the `usable` tests ask for direct gradient sinks)
+            def member(j, z, training=k.net.training):
+                s = self._glow_vec_step_at(j, z)
+                return s if s is not None and s[0].initialized and s[2].net.training == training else None
+            run = self._collect(i, z, 1, 3, member)
+            if FUSED.glow_flow_nograd_usable(z, run):              # density evaluation: no autograd node at all
+                return (*FUSED.glow_flow_vec_nograd(z, ld, run), 3 * len(run))
+            if FUSED.glow_flow_vec_usable(z, run):                 # the whole run of steps: one launch per direction
+                return (*FUSED.glow_flow_vec(z, ld, run), 3 * len(run))
+        if _vector_coupling(k) and FUSED.glow_step_vec_usable(z, k.net):
+            self._actnorm_init(a, z)
+            return (*FUSED.glow_step_vec(z, ld, a, c, k), 3)                      # the whole step: one launch
+        return self._head_step(a, c, k, z, ld)
+
+    def _glow_step_w(self, i, z, ld):
+        """image data with more channels than the in-kernel PLU head takes (9 .. 64): head in one MFMA launch"""
+        m = self._glow_triple_at(i, z) if GLOW_HEAD_W_ON and z.dim() == 4 and z.shape[1] > NF.HEAD_MAX_C else None
+        if m is not None:
+            return self._head_step(*m, z, ld)
+
+    @staticmethod
+    def _actnorm_init(a, z):
+        if not a.initialized:
+            NF.actnorm_init_(z, a.log_scale, a.bias, a.eps)
+            a.initialized = True
+
+    def _head_step(self, a, c, k, z, ld):
+        """one flow step as the fused head (ActNorm + 1x1 + the coupling's split-gather in one launch) and the coupling's own launches.
+        Up to HEAD_MAX_C channels the head factors the PLU weight in the kernel (functional.glow_head); above, it multiplies by the
+        weight the model's batched PLU pre-pass assembled, on the MFMA units (functional.glow_head_w) -- or declines where that head
+        does not serve."""
+        wide = z.shape[1] > NF.HEAD_MAX_C
+        if wide and (c._W_eff is None or k.mode not in (N.SPLIT_CHANNEL, N.SPLIT_CHECKER) or not NF.glow_head_w_usable(z, k.mode)):
+            return None
+        self._actnorm_init(a, z)
+        # image data: the head's forward rides the prologue of the coupling's chain launch when that launch follows (round 5) ...
+        from . import fused_conv as FC
+        defer = (HEAD_IN_CHAIN and z.dim() == 4 and type(k) is AffineCoupling and isinstance(k.net, ConvNet) and z.is_contiguous()
+                 and FC.head_in_chain_ok(k.net, z, k.mode))
+        # ... and its data gradient the prologue of the PREVIOUS step's backward chain launch, when z is that launch's output (round 6)
+        bwd_defer = defer and NF.from_fused_coupling(z)
+        if wide:
+            W, holder, idx = c._W_eff
+            h, z1c, ld = NF.glow_head_w(z, ld, a.log_scale, a.bias, W, c.log_s, holder, idx, k.mode, k.odd, defer=defer, bwd_defer=bwd_defer)
+        else:
+            h, z1c, ld = NF.glow_head(z, ld, a.log_scale, a.bias, c.P, c.L, c.U, c.L_mask, c.U_mask, c.sign_s, c.log_s, k.mode, k.odd,
+                                      bwd_defer=bwd_defer, defer=defer)
+        z, ld = k.couple(h, z1c, ld)
+        if defer and NF.flush_pending_head(h):
+            raise RuntimeError('a deferred Glow head was not performed by its coupling launch')
+        return z, ld, 3
+
+    def _flowpp_pair(self, i, z, ld):
+        m = self._flowpp_pair_at(i, z)
+        if m is not None:                                          # coupling + next ActNorm
+            return (*FUSED.flowpp_coupling_vec(z, ld, m[0], post=m[1]), 2)
+
+    def _layer(self, i, z, ld):
+        return (*self.layers[i](z, ld), 1)
+
+    _FORWARD = (_planar, _resflow, _realnvp_eval, _maf_eval, _bn_step, _glow_step, _glow_step_w, _flowpp_pair, _layer)
 
     def forward(self, z, log_df_dz):
-        L, n, i = self.layers, len(self.layers), 0
+        i, n = 0, len(self.layers)
         while i < n:
-            run = self._planar_run(i, z, 1) if self._fuse_now else []
-            if run:                                                # the run of planar layers: projection + one launch
-                z, log_df_dz = NF.planar_flow(z, log_df_dz, run)
-                i += len(run)
-                continue
-            run = self._resflow_run(i, z, 1) if self._fuse_now else []
-            if run:                                                # the run of residual blocks: a handful of launches whatever its length
-                z, log_df_dz = NF.resflow_flow(z, log_df_dz, run, self._resflow_draws, self._resflow_seed)
-                i += 2 * len(run)
-                continue
-            run = self._realnvp_eval_run_at(i, z) if not torch.is_grad_enabled() else None
-            if run is not None:                                    # density evaluation: the run in one launch, no exchange
-                z, log_df_dz = FUSED.realnvp_flow_vec_eval(z, log_df_dz, run)
-                i += 2 * len(run)
-                continue
-            if self._maf_pair_at(i, z) and FUSED.maf_step_eval_usable(z, L[i], L[i + 1]):
-                z, log_df_dz = FUSED.maf_step_eval(z, log_df_dz, L[i], L[i + 1])   # density evaluation: one launch, no exchange
-                i += 2
-                continue
-            if self._bn_step_at(i, z):
-                a, k = L[i], L[i + 1]
-                run = self._realnvp_run_at(i, z)
-                if run is not None:                                # the whole run of steps: one launch per direction
-                    z, log_df_dz = FUSED.realnvp_flow_vec(z, log_df_dz, run)
-                    i += 2 * len(run)
-                    continue
-                if (type(k) is AffineCoupling and k.mode == N.SPLIT_1D and isinstance(k.net, MLP)
-                        and FUSED.realnvp_step_vec_usable(z, a, k.net)):
-                    z, log_df_dz = FUSED.realnvp_step_vec(z, log_df_dz, a, k)        # the whole step: one launch
-                elif type(k) is AffineCoupling:
-                    h, z1c, log_df_dz = NF.flowbn_head(z, log_df_dz, a, k.mode, k.odd, gather=True)
-                    z, log_df_dz = k.couple(h, z1c, log_df_dz)
-                elif FUSED.maf_step_usable(z, a, k):
-                    run = self._maf_run_at(i, z)
-                    if run is not None:                            # the run as one autograd node, one fold for all steps
-                        z, log_df_dz = FUSED.maf_flow_vec(z, log_df_dz, run)
-                        i += 2 * len(run)
-                        continue
-                    z, log_df_dz = FUSED.maf_step_vec(z, log_df_dz, a, k)            # the whole step: one launch
-                else:
-                    h, log_df_dz = NF.flowbn_head(z, log_df_dz, a)
-                    z, log_df_dz = k(h, log_df_dz)
-                i += 2
-            elif self._glow_step_at(i, z):
-                a, c, k = L[i], L[i + 1], L[i + 2]
-                run = self._glow_run_at(i, z)
-                if run is not None and run[0] == 'nograd':
-                    z, log_df_dz = FUSED.glow_flow_vec_nograd(z, log_df_dz, run[1])
-                    i += 3 * len(run[1])
-                    continue
-                if run is not None:                                # the whole run of steps: one launch per direction
-                    z, log_df_dz = FUSED.glow_flow_vec(z, log_df_dz, run)
-                    i += 3 * len(run)
-                    continue
-                if not a.initialized:
-                    NF.actnorm_init_(z, a.log_scale, a.bias, a.eps)
-                    a.initialized = True
-                if k.mode == N.SPLIT_1D and isinstance(k.net, MLP) and FUSED.glow_step_vec_usable(z, k.net):
-                    z, log_df_dz = FUSED.glow_step_vec(z, log_df_dz, a, c, k)        # the whole step: one launch
-                else:
-                    # (image data: the head rides the chain launches of the fused couplings on either side, as the MFMA head below)
-                    from . import fused_conv as FC
-                    defer = (HEAD_IN_CHAIN and z.dim() == 4 and type(k) is AffineCoupling and isinstance(k.net, ConvNet)
-                             and z.is_contiguous() and FC.head_in_chain_ok(k.net, z, k.mode))
-                    h, z1c, log_df_dz = NF.glow_head(z, log_df_dz, a.log_scale, a.bias, c.P, c.L, c.U, c.L_mask,
-                                                     c.U_mask, c.sign_s, c.log_s, k.mode, k.odd,
-                                                     bwd_defer=defer and NF.from_fused_coupling(z), defer=defer)
-                    z, log_df_dz = k.couple(h, z1c, log_df_dz)
-                    if defer and NF.flush_pending_head(h):
-                        raise RuntimeError('a deferred Glow head was not performed by its coupling launch')
-                i += 3
-            elif self._glow_step_w_at(i, z):                      # image data, 9 .. 64 channels: head in one MFMA launch
-                a, c, k = L[i], L[i + 1], L[i + 2]
-                if not a.initialized:
-                    NF.actnorm_init_(z, a.log_scale, a.bias, a.eps)
-                    a.initialized = True
-                W, holder, idx = c._W_eff
-                # the head's forward rides the prologue of the coupling's chain launch when that launch follows (round 5)
-                from . import fused_conv as FC
-                defer = (HEAD_IN_CHAIN and type(k) is AffineCoupling and isinstance(k.net, ConvNet) and z.is_contiguous()
-                         and FC.head_in_chain_ok(k.net, z, k.mode))
-                # ... and its data gradient the prologue of the PREVIOUS step's backward chain launch, when z is that launch's output (round 6)
-                bwd_defer = defer and NF.from_fused_coupling(z)
-                h, z1c, log_df_dz = NF.glow_head_w(z, log_df_dz, a.log_scale, a.bias, W, c.log_s, holder, idx, k.mode, k.odd, defer=defer,
-                                                   bwd_defer=bwd_defer)
-                z, log_df_dz = k.couple(h, z1c, log_df_dz)
-                if defer and NF.flush_pending_head(h):
-                    raise RuntimeError('a deferred Glow head was not performed by its coupling launch')
-                i += 3
-            elif self._flowpp_pair_at(i, z):
-                z, log_df_dz = FUSED.flowpp_coupling_vec(z, log_df_dz, L[i], post=L[i + 1])   # coupling + next ActNorm
-                i += 2
-            else:
-                z, log_df_dz = L[i](z, log_df_dz)
-                i += 1
+            for route in self._FORWARD:                            # in priority order; _layer serves whatever the others decline
+                out = route(self, i, z, log_df_dz)
+                if out is not None:
+                    z, log_df_dz, used = out
+                    i += used
+                    break
         return z, log_df_dz
 
-    def _glow_inverse_run_ending_at(self, i, z):
-        """the maximal run of fused-step-capable Glow steps on (N, 2 | 4) data whose LAST layer is layer i (in forward order), or
-        None: its inverse is one launch per step, or one for the whole run (fused.glow_flow_vec_inverse)"""
-        L, run, j = self.layers, [], i
-        if z.dim() != 2 or torch.is_grad_enabled() and z.requires_grad:
+    # ---- inverse routes: layer i is the LAST layer of what a route serves; all of them run under no_grad (see backward) ----------------
+    def _planar_inverse(self, i, z, ld):
+        run = self._planar_run(i, z, -1) if self._fuse_now else []
+        if run:                                                    # the run of planar layers: one bisection launch (or 3 per layer)
+            return (*NF.planar_inverse(z, ld, run)[:2], len(run))
+
+    def _resflow_inverse(self, i, z, ld):
+        run = self._resflow_run(i, z, -1) if (self._fuse_now and z.dim() == 2
+                                              and z.shape[0] <= N.header_constant('NF_RESFLOW_INV_WG_MAX_ROWS')) else []
+        if run:                                                    # the run of residual blocks: the whole inverse in one workgroup
+            return (*NF.resflow_inverse(z, ld, run, self._resflow_draws, self._resflow_seed)[:2], 2 * len(run))
+
+    def _glow_inverse(self, i, z, ld):
+        """the run of fused-step-capable Glow steps on (N, 2 | 4) data that ends at layer i: one launch per step, or one for the run"""
+        if z.dim() != 2:
             return None
-        while j >= 2 and self._glow_step_at(j - 2, z):
-            a, c, k = L[j - 2], L[j - 1], L[j]
-            if not (k.mode == N.SPLIT_1D and isinstance(k.net, MLP) and not k._backward_hooks):
-                break
-            run.append((a, c, k))
-            j -= 3
-        run.reverse()
-        return run if run and FUSED.glow_inverse_usable(z, run) else None
 
-    def _realnvp_pair_at(self, j, z):
-        """[flow BatchNorm(affine=False), AffineCoupling(MLP)] at layers j, j + 1 on (N, 2 | 4) data, any mode, no hooks"""
-        L = self.layers
-        if not (self._fuse_now and z.is_cuda and z.dim() == 2 and j >= 0 and j + 1 < len(L)):
-            return False
-        a, k = L[j], L[j + 1]
-        if not (type(a) is BatchNorm and not isinstance(a.log_gamma, nn.Parameter) and type(k) is AffineCoupling
-                and k.mode == N.SPLIT_1D and isinstance(k.net, MLP)):
-            return False
-        return not (a._forward_hooks or k._forward_hooks or a._forward_pre_hooks or k._forward_pre_hooks)
+        def member(j, z):
+            s = self._glow_vec_step_at(j, z)
+            # (the coupling's backward hooks alone: those of the ActNorm and the 1x1 are not looked at here -- kept as found)
+            return s if s is not None and _unhooked(backward=(s[2], )) else None
+        run = self._collect(i, z, -1, 3, member)
+        if run and FUSED.glow_inverse_usable(z, run):
+            return (*FUSED.glow_flow_vec_inverse(z, ld, run), 3 * len(run))
 
-    def _maf_pair_at(self, j, z):
-        """[flow BatchNorm(affine=False), AutoregressiveTransfrom] at layers j, j + 1 on (N, D) data, any mode, no hooks"""
-        L = self.layers
-        if not (self._fuse_now and z.is_cuda and z.dim() == 2 and j >= 0 and j + 1 < len(L)):
-            return False
-        a, k = L[j], L[j + 1]
-        if not (type(a) is BatchNorm and not isinstance(a.log_gamma, nn.Parameter) and type(k) is AutoregressiveTransfrom):
-            return False
-        return not (a._forward_hooks or k._forward_hooks or a._forward_pre_hooks or k._forward_pre_hooks)
+    def _realnvp_inverse(self, i, z, ld):
+        run = self._collect(i, z, -1, 2, self._realnvp_any_mode_at)
+        if run and FUSED.realnvp_inverse_usable(z, run):
+            return (*FUSED.realnvp_flow_vec_inverse(z, ld, run), 2 * len(run))
 
-    def _realnvp_inverse_run_ending_at(self, i, z):
-        L, run, j = self.layers, [], i
-        if z.dim() != 2 or torch.is_grad_enabled() and z.requires_grad:
-            return None
-        while self._realnvp_pair_at(j - 1, z):
-            run.append((L[j - 1], L[j]))
-            j -= 2
-        run.reverse()
-        return run if run and FUSED.realnvp_inverse_usable(z, run) else None
+    def _maf_inverse(self, i, z, ld):
+        m = self._bn_pair_at(i - 1, z, False, _autoregressive)
+        if m is not None and FUSED.maf_step_inverse_usable(z, *m):
+            # one launch per step; with device draws it reads a mask set per pass (the two names are the two mask sources of one body)
+            inverse = FUSED.maf_step_inverse_drawn if FUSED.maf_device_draws(m[1]) else FUSED.maf_step_inverse
+            return (*inverse(z, ld, *m), 2)
 
-    def _realnvp_eval_run_at(self, i, z):
-        L, run, j = self.layers, [], i
-        while self._realnvp_pair_at(j, z):
-            run.append((L[j], L[j + 1]))
-            j += 2
-        return run if run and FUSED.realnvp_eval_usable(z, run) else None
+    def _layer_inverse(self, i, z, ld):
+        return (*self.layers[i].backward(z, ld), 1)
+
+    _INVERSE = (_planar_inverse, _resflow_inverse, _glow_inverse, _realnvp_inverse, _maf_inverse, _layer_inverse)
 
     def backward(self, z, log_df_dz):
         """INVERSE flow (sampling).  The sampling kernels build no autograd graph: without a request for one the whole pass runs under
         no_grad (the reference's ``sample_y``, main.py:113, leaves autograd on and never uses the graph).  An input that requires grad --
         or the ``differentiable_inverse()`` context, for gradients of the parameters alone -- takes the graph-building form of every
-        layer's inverse instead (inverse_grad.py: the reference's formulas over the engine's own conditioners and gathers)."""
+        layer's inverse instead (inverse_grad.py: the reference's formulas over the engine's own conditioners and gathers).
+        Invariant: past the first branch below grad is off, so no inverse route has an autograd case to tell apart."""
         if torch.is_grad_enabled():
             from . import inverse_grad as IG
             if IG.wanted(z, log_df_dz):
@@ -353,39 +356,12 @@ class Compose(nn.Module):
                 return self.backward(z, log_df_dz)
         i = len(self.layers) - 1
         while i >= 0:
-            run = self._planar_run(i, z, -1) if self._fuse_now else []
-            if run:                                                # the run of planar layers: one bisection launch (or 3 per layer)
-                z, log_df_dz, _ = NF.planar_inverse(z, log_df_dz, run[::-1])
-                i -= len(run)
-                continue
-            run = self._resflow_run(i, z, -1) if (self._fuse_now and z.dim() == 2
-                                                  and z.shape[0] <= N.header_constant('NF_RESFLOW_INV_WG_MAX_ROWS')) else []
-            if run:                                                # the run of residual blocks: the whole inverse in one workgroup
-                z, log_df_dz, _ = NF.resflow_inverse(z, log_df_dz, run, self._resflow_draws, self._resflow_seed)
-                i -= 2 * len(run)
-                continue
-            run = self._glow_inverse_run_ending_at(i, z)
-            if run is not None:
-                z, log_df_dz = FUSED.glow_flow_vec_inverse(z, log_df_dz, run)
-                i -= 3 * len(run)
-                continue
-            run = self._realnvp_inverse_run_ending_at(i, z)
-            if run is not None:
-                z, log_df_dz = FUSED.realnvp_flow_vec_inverse(z, log_df_dz, run)
-                i -= 2 * len(run)
-                continue
-            if self._maf_pair_at(i - 1, z) and not (torch.is_grad_enabled() and z.requires_grad) \
-                    and FUSED.maf_step_inverse_drawn_usable(z, self.layers[i - 1], self.layers[i]):
-                z, log_df_dz = FUSED.maf_step_inverse_drawn(z, log_df_dz, self.layers[i - 1], self.layers[i])    # device draws: a mask set per pass
-                i -= 2
-                continue
-            if self._maf_pair_at(i - 1, z) and not (torch.is_grad_enabled() and z.requires_grad) \
-                    and FUSED.maf_step_inverse_usable(z, self.layers[i - 1], self.layers[i]):
-                z, log_df_dz = FUSED.maf_step_inverse(z, log_df_dz, self.layers[i - 1], self.layers[i])
-                i -= 2
-                continue
-            z, log_df_dz = self.layers[i].backward(z, log_df_dz)
-            i -= 1
+            for route in self._INVERSE:
+                out = route(self, i, z, log_df_dz)
+                if out is not None:
+                    z, log_df_dz, used = out
+                    i -= used
+                    break
         return z, log_df_dz
 
 
