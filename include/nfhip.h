@@ -1169,6 +1169,29 @@ int nf_flowpp_img_pre_bwd(const float* x, const float* a, const float* ln1_g, co
 int nf_sample_data(int kind, float* out, int64_t n, int per_sample, int64_t seed, const int64_t* step, nf_stream_t stream);
 int nf_sample_advance(int64_t* step, nf_stream_t stream);
 
+/* ---- device-resident data sets (csrc/dataset.hip)  flows/dataset.py:53-127 (FlowDataLoader); replaces the host-side batch assembly
+ * and the per-step H2D copy main.py:79 ----
+ * The set lives in device memory; one launch gathers this rank's batch of the step read from `step` (device int64, NULL = 0;
+ * nf_sample_advance moves it on, so a captured graph walks through batches and epochs by itself).
+ * Schedule  dataset.py:111-117: a pass serves batches while N > iter + B, i.e. E = (N - 1) / stride steps of `stride` = world * B
+ *   positions (the tail is dropped, and the last full batch too where stride divides N); step s -> epoch = s / E, k = s % E; the rank takes
+ *   positions k * stride + offset + j, j < B, `offset` = rank * B.
+ * Order  dataset.py:104-106 (np.random.shuffle once per pass): here index = perm(seed, epoch, position), a bijection of [0, N) -- an
+ *   8-round balanced Feistel network on Philox4x32-10 with cycle walking (csrc/dataset.hip; data.dataset_perm is the same function in
+ *   numpy, bit for bit); shuffle == 0: index = position.
+ * idx_out (B, int64, may be NULL) receives the indices used.
+ * NF_E_BADARG before any launch: data or out NULL, N <= 0, N >= 2^31, B <= 0, E < 1, E > (N - 1) / stride, offset < 0,
+ *   offset + B > stride.                                                                                                          */
+/* images  dataset.py:119-122, :71: data uint8 (N, H, W, C) -> out float32 (B, C, H + 2 pad, W + 2 pad) = (float)v / 255.0f (a true
+ * division, bit-equal to numpy's float32 / 255.0), HWC -> CHW, the pad ring written as zeros on every call (transforms.Pad).
+ * Also NF_E_BADARG: H, W, C < 1, pad < 0, W * C > 32736 (one input row is staged in LDS).                                           */
+int nf_dataset_gather_u8(const uint8_t* data, float* out, int64_t N, int H, int W, int C, int pad, int64_t B, int64_t stride,
+                         int64_t offset, int64_t E, int64_t seed, int shuffle, const int64_t* step, int64_t* idx_out,
+                         nf_stream_t stream);
+/* rows  dataset.py:124-125: data float32 (N, D) -> out (B, D).  Also NF_E_BADARG: D < 1.                                            */
+int nf_dataset_gather_f32(const float* data, float* out, int64_t N, int64_t D, int64_t B, int64_t stride, int64_t offset, int64_t E,
+                          int64_t seed, int shuffle, const int64_t* step, int64_t* idx_out, nf_stream_t stream);
+
 /* ---- NLL of the training harness  main.py:49-51, :85 -------------------------------------------------------------
  * loss[0] += -(1/B) * sum_b ( -0.5*|z_b|^2 - 0.5*D*log(2 pi) + ld[b] )   (caller zero-fills loss)            */
 int nf_nll_loss(const float* z, const float* ld, float* loss, int64_t B, int64_t D, nf_stream_t stream);

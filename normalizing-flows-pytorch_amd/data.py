@@ -118,3 +118,164 @@ class DeviceSampler:
         N.call('nf_sample_data', self.kind, self.out.data_ptr(), self.batch, self.per, self.seed, self.step.data_ptr(), N.stream())
         N.call('nf_sample_advance', self.step.data_ptr(), N.stream())
         return self.out
+
+
+# ---- device-resident data sets (csrc/dataset.hip): the reference loader's batch sequence, gathered where it is consumed ---------------
+N_DATASET_SIZE = 65536          # dataset.py:10: the fixed size of the reference's toy sets
+DS_ROUNDS = 8                   # Feistel rounds (csrc/dataset.hip NF_DS_ROUNDS)
+DS_WALK = 155                   # bound of the cycle walk: (3/4)^155 < 2^-64 (NF_DS_WALK); beyond it the position itself is served
+DS_KEY = 0x510e527f             # key constant that sets the permutation's Philox stream apart (NF_DS_KEY)
+
+
+def _philox_word0(c0, c1, c2, c3, k0, k1):
+    """word 0 of Philox4x32-10 (csrc/nf_philox.h) on uint64 arrays / scalars holding 32-bit words"""
+    M0, M1, W0, W1, m32 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), 0x9E3779B9, 0xBB67AE85, np.uint64(0xFFFFFFFF)
+    c0 = np.asarray(c0, dtype=np.uint64)
+    c1, c2, c3 = (np.broadcast_to(np.asarray(c, dtype=np.uint64), c0.shape) for c in (c1, c2, c3))
+    for r in range(10):
+        p0, p1 = M0 * c0, M1 * c2
+        ka, kb = np.uint64((k0 + r * W0) & 0xFFFFFFFF), np.uint64((k1 + r * W1) & 0xFFFFFFFF)
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ ka, p1 & m32, (p0 >> np.uint64(32)) ^ c3 ^ kb, p0 & m32
+    return c0
+
+
+def dataset_perm(seed, epoch, pos, N, rounds=DS_ROUNDS):
+    """index in [0, N) served at position ``pos`` of pass ``epoch`` (ints, or arrays that broadcast): for every (seed, epoch) a bijection
+    of [0, N).
+    A balanced Feistel network over 2h bits, h = max(1, ceil(bits(N - 1) / 2)): (L, R) -> (R, L ^ F(R, round)) with F = word 0 of
+    Philox4x32-10(counter (R, round, epoch lo, epoch hi), key (seed lo, seed hi ^ DS_KEY)) masked to h bits, applied again while the
+    result is >= N (cycle walking, at most DS_WALK further times).  Integers only: the same function as nf_ds_index of
+    csrc/dataset.hip, bit for bit.  ``rounds`` exists for the tests that tell 8 rounds from fewer."""
+    N = int(N)
+    if not 0 < N < 1 << 31:
+        raise ValueError('dataset_perm: N must lie in [1, 2^31), got %d' % N)
+    pos = np.asarray(pos, dtype=np.int64)
+    if pos.size and (pos.min() < 0 or pos.max() >= N):
+        raise ValueError('dataset_perm: positions must lie in [0, N)')
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    epoch = np.asarray(epoch).astype(np.uint64) if isinstance(epoch, np.ndarray) else np.uint64(int(epoch) & 0xFFFFFFFFFFFFFFFF)
+    shape = np.broadcast(pos, epoch).shape
+    start = np.broadcast_to(pos, shape).astype(np.uint64).reshape(-1)
+    epoch = np.broadcast_to(epoch, shape).reshape(-1)
+    bits = (N - 1).bit_length()
+    h = 1 if bits < 2 else (bits + 1) // 2
+    mask, hh = np.uint64((1 << h) - 1), np.uint64(h)
+    k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) ^ DS_KEY
+
+    def feistel(x, e):
+        L, R, e_lo, e_hi = x >> hh, x & mask, e & np.uint64(0xFFFFFFFF), e >> np.uint64(32)
+        for r in range(rounds):
+            L, R = R, L ^ (_philox_word0(R, r, e_lo, e_hi, k0, k1) & mask)
+        return (L << hh) | R
+    x = feistel(start, epoch)
+    for _ in range(DS_WALK):
+        out = np.nonzero(x >= np.uint64(N))[0]
+        if out.size == 0:
+            break
+        x[out] = feistel(x[out], epoch[out])
+    x = np.where(x >= np.uint64(N), start, x)
+    return x.astype(np.int64).reshape(shape)
+
+
+class DeviceDataset:
+    """A data set held in DEVICE memory that serves the reference loader's batch sequence (flows/dataset.py:53-127) with no host work
+    per step: ``next()`` gathers this rank's batch of the current step into one static tensor and advances the step, two launches that
+    a hipGraph can capture (FlowTrainer(sampler=...)); a replay walks through the batches and the epochs by itself.
+
+    ``source``  uint8 (N, H, W) or (N, H, W, C), array or tensor: the image form -- out (B, C, H + 2 pad, W + 2 pad) = uint8 / 255, HWC ->
+                CHW, a zero ring of ``pad`` pixels (MNIST: pad = 2), dims = (C, H + 2 pad, W + 2 pad), dtype 'image' (dataset.py:67-79,
+                :119-122);  float32 (N, D): the row form -- out (B, D), dims = (D, ), dtype '2d' / '3d' (dataset.py:80-99, :124-125).
+                Uploaded once.
+    Schedule    dataset.py:111-117: a pass has steps_per_epoch = (N - 1) // (world * batch) steps (the tail is dropped, and the last full
+                batch where world * batch divides N); step s is step s % E of pass s // E; rank r takes positions
+                k * world * batch + r * batch + j of the pass's order, so the ranks of one step hold disjoint samples of ONE permutation
+                (the rank is not folded into the seed).  N <= world * batch is refused.
+    Order       ``shuffle``: index = dataset_perm(seed, pass, position), evaluated in the gather kernel -- no index array, no reshuffle
+                launch (the reference: np.random.shuffle per pass); otherwise the identity.
+    ``device``  None builds a host-only object: ``indices`` / ``host_batch`` work, ``next()`` does not."""
+
+    def __init__(self, source, batch, pad=0, seed=0, shuffle=True, device='cuda', rank=None, world=None):
+        arr = source.detach().cpu().numpy() if isinstance(source, torch.Tensor) else np.asarray(source)
+        if arr.dtype == np.uint8 and arr.ndim in (3, 4):
+            arr = arr.reshape(arr.shape + (1, )) if arr.ndim == 3 else arr
+            self.image = True
+        elif arr.dtype == np.float32 and arr.ndim == 2:
+            self.image = False
+        else:
+            raise ValueError('DeviceDataset takes uint8 (N, H, W[, C]) images or float32 (N, D) rows, got %s %s' % (arr.dtype, arr.shape))
+        if min(arr.shape) < 1:
+            raise ValueError('DeviceDataset: empty source %s' % (arr.shape, ))
+        self.host = np.ascontiguousarray(arr)
+        self.n, self.batch, self.pad = int(arr.shape[0]), int(batch), int(pad)
+        if self.pad < 0 or (self.pad and not self.image):
+            raise ValueError('pad is a non-negative ring of pixels around images')
+        if rank is None or world is None:
+            import torch.distributed as _d
+            on = _d.is_available() and _d.is_initialized()
+            rank = (_d.get_rank() if on else 0) if rank is None else rank
+            world = (_d.get_world_size() if on else 1) if world is None else world
+        self.rank, self.world = int(rank), int(world)
+        if self.batch < 1 or self.world < 1 or not 0 <= self.rank < self.world:
+            raise ValueError('DeviceDataset: batch %d, rank %d of %d' % (self.batch, self.rank, self.world))
+        self.stride, self.offset = self.world * self.batch, self.rank * self.batch
+        if self.n >= 1 << 31:
+            raise ValueError('DeviceDataset holds fewer than 2^31 samples')
+        if self.n <= self.stride:
+            raise ValueError('a data set of %d samples serves no batch of %d x %d: the loader needs N > world * batch (dataset.py:113)'
+                             % (self.n, self.world, self.batch))
+        self.steps_per_epoch = (self.n - 1) // self.stride
+        self.seed, self.shuffle = int(seed) & 0x7FFFFFFFFFFFFFFF, bool(shuffle)
+        if self.image:
+            _, H, W, C = arr.shape
+            self.dims, self.dtype = (C, H + 2 * self.pad, W + 2 * self.pad), 'image'
+        else:
+            self.dims, self.dtype = (int(arr.shape[1]), ), '%dd' % arr.shape[1]
+        self.data = self.out = self.step = self.last_indices = None
+        if device is not None:
+            from . import _native as N
+            self._N = N
+            self.data = torch.from_numpy(self.host).to(device)
+            self.out = torch.empty((self.batch, ) + self.dims, dtype=torch.float32, device=device)
+            self.step = torch.zeros(1, dtype=torch.int64, device=device)
+            self.last_indices = torch.zeros(self.batch, dtype=torch.int64, device=device)
+
+    @classmethod
+    def toy(cls, name, batch, seed=0, n=N_DATASET_SIZE, **kw):
+        """the reference's fixed toy set of N_DATASET_SIZE points (dataset.py:10-50, :80-99), built ONCE from data.GENERATORS[name] --
+        the reference draws it again at every pass (:113-114 call _initialize) --; ``seed`` seeds the points and the order alike."""
+        if name not in GENERATORS or name == 'cifar':
+            raise ValueError('no toy set named %r' % (name, ))
+        return cls(GENERATORS[name](int(n), np.random.default_rng(seed)), batch, seed=seed, **kw)
+
+    @classmethod
+    def from_npz(cls, path, key, batch, **kw):
+        """an array a user has on disk: ``np.load(path)[key]``, uint8 images or float32 rows"""
+        with np.load(path) as f:
+            return cls(f[key], batch, **kw)
+
+    def next(self):
+        if self.data is None:
+            raise RuntimeError('this DeviceDataset was built with device=None: it has no device copy to gather from')
+        N, a = self._N, (self.n, ) + (self.host.shape[1:] if self.image else (self.host.shape[1], ))
+        tail = (self.batch, self.stride, self.offset, self.steps_per_epoch, self.seed, int(self.shuffle), self.step.data_ptr(),
+                self.last_indices.data_ptr(), N.stream())
+        if self.image:
+            N.call('nf_dataset_gather_u8', self.data.data_ptr(), self.out.data_ptr(), a[0], a[1], a[2], a[3], self.pad, *tail)
+        else:
+            N.call('nf_dataset_gather_f32', self.data.data_ptr(), self.out.data_ptr(), a[0], a[1], *tail)
+        N.call('nf_sample_advance', self.step.data_ptr(), N.stream())
+        return self.out
+
+    def indices(self, step):
+        """(batch, ) int64: the samples this rank is served at ``step`` (numpy; what the kernel writes to ``last_indices``)"""
+        epoch, k = divmod(int(step), self.steps_per_epoch)
+        pos = k * self.stride + self.offset + np.arange(self.batch, dtype=np.int64)
+        return dataset_perm(self.seed, epoch, pos, self.n) if self.shuffle else pos
+
+    def host_batch(self, step):
+        """the batch of ``step`` as the reference builds it on the host (dataset.py:116-125), a float32 torch tensor"""
+        rows = self.host[self.indices(step)]
+        if not self.image:
+            return torch.from_numpy(rows)
+        x, p = np.transpose(rows.astype('float32') / 255.0, (0, 3, 1, 2)), self.pad
+        return torch.from_numpy(np.ascontiguousarray(np.pad(x, ((0, 0), (0, 0), (p, p), (p, p))).astype(np.float32)))

@@ -300,7 +300,8 @@ class FlowTrainer:
         self.sync_stats = bool(sync_stats)
         if self.sync_stats:
             graph = False
-        self.sampler = sampler      # data.DeviceSampler: train_on_batch() without a batch draws one on the device, inside the graph
+        self.sampler = sampler      # data.DeviceSampler / data.DeviceDataset (next(), .out, .step): train_on_batch() without a batch draws or
+                                    # gathers one on the device, inside the graph
         on_gpu = next(net.parameters()).is_cuda
         if graph and any(getattr(m_, 'masks_redrawn_per_call', False) and getattr(m_, 'draws', 'host') != 'device' for m_ in net.modules()):
             # MADE re-draws its masks from the host's np.random on every call (flows/maf.py:50,72); for D > 2 the draw varies, and a
@@ -496,7 +497,7 @@ class FlowTrainer:
         a grid exchange (sticky pinned error word, no synchronisation: at most one step late)."""
         from . import _native as N
         if y is None and self.sampler is None:
-            raise ValueError('train_on_batch() without a batch needs FlowTrainer(..., sampler=data.DeviceSampler(...))')
+            raise ValueError('train_on_batch() without a batch needs FlowTrainer(..., sampler=data.DeviceSampler(...) or data.DeviceDataset(...))')
         if y is not None and y.is_cuda and y.device.index != torch.cuda.current_device():
             # a model / batch on another GPU than the current one (net.to('cuda:1') without torch.cuda.set_device works in the reference):
             # the launches must go to THAT device's stream and read its copy of the library's globals
