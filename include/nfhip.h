@@ -469,6 +469,9 @@ int nf_conv_bn_usable(int64_t B, int I, int O, int H, int W, int ksize);
  * nf_conv_bn_bwd (data pass); same results to fp32 rounding.  Switches for tests and A/B runs (-1 = keep): on, min_pixels, nblk
  * (pixel blocks per wave: 0 automatic, 1, 2).  Environment: NF_CONV_BULK=0 (off).                                                  */
 int nf_conv_bulk_config(int on, int64_t min_pixels, int nblk);
+/* 1 when nf_conv_bn_wgrad_multi / _table run a launch of this shape on the pixel-contraction kernel of csrc/conv_bulk.hip (3x3, O = 32,
+ * I <= 32, W = 8 or 16 and H*W >= 16, at the current nf_conv_bulk_config), 0 when the kernels of csrc/conv_bn.hip serve it.  Host only. */
+int nf_conv_bulk_wgrad_plan(int64_t B, int I, int O, int H, int W, int ksize);
 int nf_conv_bn_fwd(const nf_conv_desc* desc, int64_t B, int I, int O, int H, int W, int ksize, int training, float bn_eps,
                    float bn_momentum, nf_stream_t stream);
 

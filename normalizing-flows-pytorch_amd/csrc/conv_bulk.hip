@@ -727,7 +727,16 @@ __global__ void __launch_bounds__(NF_CB_THREADS) k_conv3_bulk_bwd(nf_conv_bwd_de
 //   waves 4..7 FILL: the next tile's loads (16-byte, coalesced: a lane takes four pixels of a channel), BatchNorm backward on G /
 //     BatchNorm + ReLU on the activations, the split, 8-byte LDS stores into the other frame pair; the tile after that is requested
 //     before the barrier, so its loads have a whole tile's matrix time to land.
-// ONE barrier per tile.  The workgroup walks tiles blockIdx.x + k gridDim.x of layer blockIdx.y and leaves one slab (T, O, I) and
+// The FILLERS are the late side of the barrier (tools/probes/wgrad_prof.py, profiles/r13_wgrad_phases.txt: the walkers take 2.2 - 2.3 us
+// per tile and waited 2.9 us for them), so what the filling side must NOT do is wait for anything but the tile it converts:
+//   * no load of any kind inside the tile loop but the tile loads (the descriptor's pointers are read once, into scalar registers);
+//   * the same seventeen tile loads per set on EVERY path (missing tensors and tiles beyond the end read out of range) and no way out
+//     of the loop between its two halves, so that the compiler's s_waitcnt vmcnt(N) in convert() counts the other set's loads as in flight;
+//   * one LDS round trip for constants per tile (the activations' stay in registers, the G items' are read in one batch).
+// Measured on one box, before -> after these three: tile period 5.20 -> 3.96 us (B 64, 16 x 16, sixteen layers), sixteen-layer launch
+// 68.8 -> 61.2 us, the kernel's line of a config-4 step 1.165 -> 0.890 ms.  The fillers are still the late side by about 1.5 us per tile.
+// ONE barrier per tile (one more behind an odd number of tiles: the fillers' loop runs in pairs).  The workgroup walks tiles
+// blockIdx.x + k gridDim.x of layer blockIdx.y and leaves one slab (T, O, I) and
 // its bias sums, exactly as k_conv_bn_wgrad_multi does (same slab count: nf_conv_wgrad_slabs), so nf_slab_sum is unchanged.
 // ---------------------------------------------------------------------------------------------------------------------------------
 #define NF_CBW_THREADS 512
@@ -770,6 +779,12 @@ static bool nf_cbw_geometry(NfCbwGeo& g, int64_t B, int H, int W) {
 // v[j]) on an element of an integer vector reads element 0 with this toolchain -- one dword whose value fills all four pixels.
 __device__ __forceinline__ f32x4 nf_cbw_ld128(__amdgpu_buffer_rsrc_t r, unsigned voff) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0));
+}
+// a wave-uniform pointer, pinned to scalar registers (nothing downstream can turn it back into a load)
+__device__ __forceinline__ const float* nf_cbw_pin(const float* p) {
+    const uint64_t a = (uint64_t)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+    return (const float*)(((uint64_t)hi << 32) | lo);
 }
 // four consecutive pixels of one channel -> 8 bytes in each of the three planes
 __device__ __forceinline__ void nf_cbw_put4(char* p, int plane_bytes, const float (&v)[4]) {
@@ -878,6 +893,7 @@ __global__ void __launch_bounds__(NF_CBW_THREADS) k_conv3_bulk_wgrad(NfCbwMulti 
             __syncthreads();
             NF_CBW_STAMP(0, it >= 2 && it < 10 ? 3 * (it - 2) + 2 : -1);
         }
+        if (it & 1) __syncthreads();                   // (the fillers' loop runs in pairs of tiles)
     } else {
         // =========================================== FILL ===========================================
         const int ft = tid - NF_CBW_FILL;              // 0 .. 255
@@ -891,7 +907,7 @@ __global__ void __launch_bounds__(NF_CBW_THREADS) k_conv3_bulk_wgrad(NfCbwMulti 
         // activation items: i = 256 r + ft -> channel i / NQ, item j = i % NQ -> (segment, frame row, four-pixel group)
         unsigned xoff[NF_CBW_MAXR];
         int xlds[NF_CBW_MAXR];
-        unsigned xchn = 0u;                            // 6 bits per item: channel (the BatchNorm constants are read from LDS per tile: registers hold two tiles of loads)
+        unsigned xchn = 0u;                            // 6 bits per item: channel
         unsigned xmeta = 0u;                           // 4 bits per item: class (0 never, 1 inside, 2 top halo row, 3 bottom halo row) | 4: exists; segment in xseg
         unsigned xseg = 0u;
         const int QW = g.W >> 2, RW = g.TH + 2;
@@ -919,51 +935,97 @@ __global__ void __launch_bounds__(NF_CBW_THREADS) k_conv3_bulk_wgrad(NfCbwMulti 
             xmeta |= cls << (4 * r);
             xseg |= sg << (4 * r);
         }
+        // The BatchNorm constants were read from LDS per item: nine dependent LDS round trips per tile, each behind the three stores of the
+        // item before it -- most of the 3.1 us a convert() took (profiles/r13_wgrad_phases.txt).  Now the activations' ten stay in
+        // registers for all tiles, and convert() takes the activations FIRST and then reads the twenty of its four G items in one batch,
+        // into the registers the activations' loads have just left: one round trip per tile, no register more than the loads need.
+        float kx[NF_CBW_MAXR][2];
+#pragma unroll
+        for (int r = 0; r < NF_CBW_MAXR; ++r) {
+            const int ch = (int)((xchn >> (6 * r)) & 63u);
+            kx[r][0] = cst[160 + ch]; kx[r][1] = cst[192 + ch];
+        }
         // TWO register sets: the loads of tiles k + 1 and k + 2 are in flight while tile k is walked (one set was 68 KB per compute
         // unit in flight for one round trip per tile: 2.7 TB/s; the set index is a compile-time constant: the tile loop is unrolled by two)
         f32x4 rp[2][4], rs[2][4], ro[2][4], rx[2][NF_CBW_MAXR];       // plain gradient (g_direct or g_skip), gn_src, out, activations
         unsigned gok[2] = {0u, 0u}, xok[2] = {0u, 0u};                // validity of the tile in flight
-        const float* const plain = d.g_direct != nullptr ? d.g_direct : d.g_skip;   // (the host routes layers with both elsewhere)
+        // The layer's tensors are read from the descriptor ONCE, here, into scalar registers.  `d` is a generic pointer (the device table or
+        // the kernel arguments) that the compiler can neither keep apart from the loop's LDS stores nor read through the scalar path: left
+        // inside issue(), d.gn_src / d.out and d.in were fetched again by vector loads for every tile, and the s_waitcnt vmcnt(0) in front of
+        // their use drained EVERY tile load in flight -- three exposed round trips per issue (2.0 of a 5.3 us tile period), the walkers
+        // waiting 2.9 us at the barrier (profiles/r13_wgrad_phases.txt).
+        const float* const plain = nf_cbw_pin(d.g_direct != nullptr ? d.g_direct : d.g_skip);   // (the host routes layers with both elsewhere)
+        const float* const p_src = nf_cbw_pin(d.gn_src), * const p_out = nf_cbw_pin(d.out), * const p_in = nf_cbw_pin(d.in);
+        // EVERY call issues the same 4 + 8 + NF_CBW_MAXR loads, whatever tensors the layer has and whether the tile exists (a missing tensor,
+        // a tile beyond the workgroup's last: offsets out of range -- no memory traffic, zeros), and the tile loop calls it on every path.
+        // The loads of a set return in issue order and the compiler counts them: with loads under conditions it could only count the ones it
+        // was sure of, and convert() waited (s_waitcnt vmcnt(3)) for all but three of EVERYTHING in flight -- the other set's loads, issued
+        // just before the barrier, included: one tile in flight instead of two, its round trip exposed in every convert().
         auto issue = [&](auto SET, int64_t tile) {
             constexpr int S = decltype(SET)::value;
             const int64_t P0 = tile * 128;
             const int64_t b0 = P0 >> g.lgHW;
+            const int64_t left = g.B - b0;
+            const int brem = left < 0 ? 0 : (left > 16 ? 16 : (int)left);    // samples from b0 on (a tile holds at most eight; none: beyond the end)
             const int q0 = g.SEG == 1 ? (int)(P0 & (g.HW - 1)) : 0;
             const int y0 = q0 >> g.lgW;
             const int64_t gbase = b0 * 32 * g.HW + q0;
-            const bool pv = b0 + gsg < g.B;
+            const bool pv = gsg < brem;
             gok[S] = pv ? 1u : 0u;
-            unsigned go[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) go[r] = pv ? goff0 + (unsigned)r * gcstep : NF_CB_OOB;
-            if (plain != nullptr) {
-                const __amdgpu_buffer_rsrc_t rr = nf_cb_rsrc(plain + gbase);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) rp[S][r] = nf_cbw_ld128(rr, go[r]);
-            }
-            if (has_src) {
-                const __amdgpu_buffer_rsrc_t r3 = nf_cb_rsrc(d.gn_src + gbase), r4 = nf_cb_rsrc(d.out + gbase);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { rs[S][r] = nf_cbw_ld128(r3, go[r]); ro[S][r] = nf_cbw_ld128(r4, go[r]); }
-            }
-            const __amdgpu_buffer_rsrc_t rxs = nf_cb_rsrc(d.in + b0 * I * g.HW + (int64_t)(y0 - 1) * g.W);
+            // (the activations first: convert() takes them first)
+            const __amdgpu_buffer_rsrc_t rxs = nf_cb_rsrc(p_in + b0 * I * g.HW + (int64_t)(y0 - 1) * g.W);
             const bool top = g.SEG == 1 && y0 > 0, bot = g.SEG == 1 && y0 + g.TH < g.H;
             unsigned okm = 0u;
 #pragma unroll
-            for (int r = 0; r < NF_CBW_MAXR; ++r)
-                if (r < g.nr) {                        // uniform
-                    const unsigned cls = (xmeta >> (4 * r)) & 3u;
-                    const int64_t sm = (int64_t)((xseg >> (4 * r)) & 15u);
-                    const bool ok = (cls == 1u || (cls == 2u && top) || (cls == 3u && bot)) && b0 + sm < g.B;
-                    okm |= (ok ? 1u : 0u) << r;
-                    rx[S][r] = nf_cbw_ld128(rxs, ok ? xoff[r] : NF_CB_OOB);
-                }
+            for (int r = 0; r < NF_CBW_MAXR; ++r) {   // (an item beyond g.nr has class 0: out of range)
+                const unsigned cls = (xmeta >> (4 * r)) & 3u;
+                const int sm = (int)((xseg >> (4 * r)) & 15u);
+                const bool ok = (cls == 1u || (cls == 2u && top) || (cls == 3u && bot)) && sm < brem;
+                okm |= (ok ? 1u : 0u) << r;
+                rx[S][r] = nf_cbw_ld128(rxs, ok ? xoff[r] : NF_CB_OOB);
+            }
             xok[S] = okm;
+            unsigned go[4], gp[4], gs[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                go[r] = pv ? goff0 + (unsigned)r * gcstep : NF_CB_OOB;
+                gp[r] = plain != nullptr ? go[r] : NF_CB_OOB;
+                gs[r] = has_src ? go[r] : NF_CB_OOB;
+            }
+            // (deliberate: a base is formed from a null pointer for a missing tensor and beyond the tensor for a tile past the end --
+            //  every offset on it is NF_CB_OOB, which the descriptor's window drops before any address is used)
+            const __amdgpu_buffer_rsrc_t rr = nf_cb_rsrc(plain + gbase);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) rp[S][r] = nf_cbw_ld128(rr, gp[r]);
+            const __amdgpu_buffer_rsrc_t r3 = nf_cb_rsrc(p_src + gbase), r4 = nf_cb_rsrc(p_out + gbase);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { rs[S][r] = nf_cbw_ld128(r3, gs[r]); ro[S][r] = nf_cbw_ld128(r4, gs[r]); }
         };
         auto convert = [&](auto SET) {                 // register set S -> frame pair S
             constexpr int S = decltype(SET)::value;
             char* fa = lds + S * BUF;
             char* fg = fa + 3 * PA;
+#pragma unroll
+            for (int r = 0; r < NF_CBW_MAXR; ++r)
+                if (r < g.nr && ((xmeta >> (4 * r)) & 4u)) {
+                    const bool ok = (xok[S] >> r) & 1u;
+                    const float xsc = kx[r][0], xsh = kx[r][1];
+                    float v[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        float x = rx[S][r][j];
+                        if (has_bn) x = fmaxf(fmaf(x, xsc, xsh), 0.f);
+                        v[j] = ok ? x : 0.f;
+                    }
+                    nf_cbw_put4(fa + xlds[r], PA, v);
+                }
+            float kg[4][5];                            // per G item: c1, mean, invstd, mean g, mean g xhat of channel 8 r + gch0
+            if (has_src) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int q = 0; q < 5; ++q) kg[r][q] = cst[32 * q + 8 * r + gch0];
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float v[4] = {0.f, 0.f, 0.f, 0.f};
@@ -972,8 +1034,7 @@ __global__ void __launch_bounds__(NF_CBW_THREADS) k_conv3_bulk_wgrad(NfCbwMulti 
                     for (int j = 0; j < 4; ++j) v[j] = rp[S][r][j];
                 }
                 if (has_src) {
-                    const int c = 8 * r + gch0;
-                    const float kc1 = cst[c], kmean = cst[32 + c], kinv = cst[64 + c], kmg = cst[96 + c], kmgx = cst[128 + c];
+                    const float kc1 = kg[r][0], kmean = kg[r][1], kinv = kg[r][2], kmg = kg[r][3], kmgx = kg[r][4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const float xh = (ro[S][r][j] - kmean) * kinv;
@@ -985,29 +1046,14 @@ __global__ void __launch_bounds__(NF_CBW_THREADS) k_conv3_bulk_wgrad(NfCbwMulti 
                 gsum[r] += (v[0] + v[1]) + (v[2] + v[3]);
                 nf_cbw_put4(fg + glds0 + r * 8 * NF_CBW_GCH, PG, v);
             }
-#pragma unroll
-            for (int r = 0; r < NF_CBW_MAXR; ++r)
-                if (r < g.nr && ((xmeta >> (4 * r)) & 4u)) {
-                    const bool ok = (xok[S] >> r) & 1u;
-                    const int ch = (int)((xchn >> (6 * r)) & 63u);
-                    const float xsc = cst[160 + ch], xsh = cst[192 + ch];
-                    float v[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float x = rx[S][r][j];
-                        if (has_bn) x = fmaxf(fmaf(x, xsc, xsh), 0.f);
-                        v[j] = ok ? x : 0.f;
-                    }
-                    nf_cbw_put4(fa + xlds[r], PA, v);
-                }
         };
         using S0 = std::integral_constant<int, 0>;
         using S1 = std::integral_constant<int, 1>;
         const int64_t n = tile0 < g.tiles ? (g.tiles - tile0 + tstep - 1) / tstep : 0;      // tiles of this workgroup: k -> tile0 + k tstep, set k & 1
-        if (n > 0) issue(S0{}, tile0);
-        if (n > 1) issue(S1{}, tile0 + tstep);
+        issue(S0{}, tile0);
+        issue(S1{}, tile0 + tstep);
         if (n > 0) convert(S0{});
-        if (n > 2) issue(S0{}, tile0 + 2 * tstep);
+        issue(S0{}, tile0 + 2 * tstep);
         __syncthreads();                               // frame pair 0 is complete
         for (int64_t k = 0; k < n; k += 2) {           // while the walkers are on tile k (pair 0) / k + 1 (pair 1)
             NF_CBW_STAMP(256, k >= 2 && k < 10 ? 24 + 4 * (int)(k - 2) : -1);
@@ -1017,12 +1063,13 @@ __global__ void __launch_bounds__(NF_CBW_THREADS) k_conv3_bulk_wgrad(NfCbwMulti 
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 NF_CBW_STAMP(256, k >= 2 && k < 10 ? 24 + 4 * (int)(k - 2) + 1 : -1);
 #endif
-                if (k + 3 < n) issue(S1{}, tile0 + (k + 3) * tstep);
             }
+            issue(S1{}, tile0 + (k + 3) * tstep);
             NF_CBW_STAMP(256, k >= 2 && k < 10 ? 24 + 4 * (int)(k - 2) + 2 : -1);
             __syncthreads();
             NF_CBW_STAMP(256, k >= 2 && k < 10 ? 24 + 4 * (int)(k - 2) + 3 : -1);
-            if (k + 1 >= n) break;
+            // (no way out between the halves: a path from here back to the top would be one on which set 1 was issued LAST, and the count
+            //  in front of convert(S1) would have to allow for it.  An odd n ends with an empty half; the walkers match its barrier.)
             NF_CBW_STAMP(256, k + 1 >= 2 && k + 1 < 10 ? 24 + 4 * (int)(k + 1 - 2) : -1);
             if (k + 2 < n) {
                 convert(S0{});
@@ -1030,14 +1077,14 @@ __global__ void __launch_bounds__(NF_CBW_THREADS) k_conv3_bulk_wgrad(NfCbwMulti 
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 NF_CBW_STAMP(256, k + 1 >= 2 && k + 1 < 10 ? 24 + 4 * (int)(k + 1 - 2) + 1 : -1);
 #endif
-                if (k + 4 < n) issue(S0{}, tile0 + (k + 4) * tstep);
             }
+            issue(S0{}, tile0 + (k + 4) * tstep);
             NF_CBW_STAMP(256, k + 1 >= 2 && k + 1 < 10 ? 24 + 4 * (int)(k + 1 - 2) + 2 : -1);
             __syncthreads();
             NF_CBW_STAMP(256, k + 1 >= 2 && k + 1 < 10 ? 24 + 4 * (int)(k + 1 - 2) + 3 : -1);
         }
     }
-    // (both roles have executed the same number of barriers: one before the loop, one per tile)
+    // (both roles have executed the same number of barriers: one before the loop, one per tile, one more behind an odd number of tiles)
     // ---- the four walkers' tap tiles meet in LDS (fixed order), one slab per workgroup ----
     float* red = smem;
 #pragma unroll 1
@@ -1428,7 +1475,7 @@ int nf_conv_bulk_fwd(const nf_conv_desc* desc, int64_t B, int I, int H, int W, i
 }
 
 // weight-gradient pass of up to NF_CONV_WGRAD_MAX layers of one shape (called by nf_conv_bn_wgrad_multi; 0 = the kernels of conv_bn.hip)
-int nf_conv_bulk_wgrad_plan(int64_t B, int I, int O, int H, int W, int ksize) {
+extern "C" int nf_conv_bulk_wgrad_plan(int64_t B, int I, int O, int H, int W, int ksize) {
     const int on = 1;
     // (the weight pass starts one tile count earlier than the data passes: at exactly 16 384 pixels -- config 4's per-GPU shard at
     // the 16 x 16 level, whose data passes run the persistent chain -- it measured 24.56 against 24.9 ms per step)
