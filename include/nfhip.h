@@ -1194,6 +1194,34 @@ int nf_dataset_gather_u8(const uint8_t* data, float* out, int64_t N, int H, int 
 /* rows  dataset.py:124-125: data float32 (N, D) -> out (B, D).  Also NF_E_BADARG: D < 1.                                            */
 int nf_dataset_gather_f32(const float* data, float* out, int64_t N, int64_t D, int64_t B, int64_t stride, int64_t offset, int64_t E,
                           int64_t seed, int shuffle, const int64_t* step, int64_t* idx_out, nf_stream_t stream);
+/* The same two gathers with two more options; with `dequant` = 0 and `sweep` = 0 they ARE the pair above.
+ * sweep = 1: the schedule of a held-out score, which counts every sample once (what main.py:121-127 computes for one batch, taken over
+ *   a whole set; the loader's schedule drops the tail).  A pass is E = S = ceil(N / stride) steps (1 <= E <= S is accepted); step s
+ *   serves positions (s % E) * stride + offset + j; a position >= N is served sample N - 1 (clamped: no read leaves the set) and is
+ *   invalid -- nf_logp_accumulate leaves it out.  N <= stride is allowed (N >= 1); `shuffle` permutes the valid positions per pass.
+ * dequant = 1 (images, dataset.py:119-122 with uniform noise in place of the bare / 255): byte v at byte offset b of HWC sample idx ->
+ *   q = v * 2^15 + (w >> 17),  x = ((float)q + 0.5f) * 2^-23  in (0, 1) with floor(256 x) == v  (exact in float32: 15 noise bits),
+ *   w = word b & 3 of Philox4x32-10(counter (b >> 2, idx, step lo, step hi), key (seed lo, seed hi ^ 0x9b05688c)): a pure function of
+ *   (seed, step, sample, byte), fresh on every graph replay; data.dequant_words is the same function in numpy.  The pad ring stays 0.
+ * Also NF_E_BADARG: dequant or sweep outside {0, 1}; sweep: stride >= 2^31, E > ceil(N / stride); dequant: W * C > 10901 (the noise of
+ *   one input row is staged in LDS next to its bytes).                                                                                */
+int nf_dataset_gather_u8_x(const uint8_t* data, float* out, int64_t N, int H, int W, int C, int pad, int64_t B, int64_t stride,
+                           int64_t offset, int64_t E, int64_t seed, int shuffle, int dequant, int sweep, const int64_t* step,
+                           int64_t* idx_out, nf_stream_t stream);
+int nf_dataset_gather_f32_x(const float* data, float* out, int64_t N, int64_t D, int64_t B, int64_t stride, int64_t offset, int64_t E,
+                            int64_t seed, int shuffle, int sweep, const int64_t* step, int64_t* idx_out, nf_stream_t stream);
+
+/* ---- log-likelihood accumulator of a sweep (csrc/logp.hip)  main.py:121-127 ----
+ * log p(y_b) = -1/2 |z_b|^2 - 1/2 D log(2 pi) + ld[b] from float32 z (B, D) and ld (B); the row's sum of squares and log p are formed in
+ * float64.  Two launches: rows -> logp_row (B, float64) and, where logp_f32 is not NULL, a float32 copy; then ONE workgroup reads `step`
+ * (device int64, NULL = 0), takes valid = clamp(N - ((step % S) * stride + offset), 0, B) with S = ceil(N / stride), sums the rows < valid
+ * in a fixed order in float64 and adds {sum log p, sum (log p)^2, valid} to acc[3] (the caller zero-fills it before the first step).
+ * rows_all (S * B, float64, may be NULL) receives the step's rows at [(step % S) * B + j], valid or not.
+ * No atomics and no spin loop: bit-identical from run to run and in either NF_DETERMINISTIC mode.
+ * The fold reads `step` BEFORE nf_sample_advance bumps it: launch  gather -> net -> nf_logp_accumulate -> nf_sample_advance.
+ * NF_E_BADARG before any launch: z, ld, logp_row or acc NULL, B, D, N <= 0, N or stride >= 2^31, offset < 0, offset + B > stride.     */
+int nf_logp_accumulate(const float* z, const float* ld, double* logp_row, float* logp_f32, double* rows_all, double* acc, int64_t B,
+                       int64_t D, int64_t N, int64_t stride, int64_t offset, const int64_t* step, nf_stream_t stream);
 
 /* ---- NLL of the training harness  main.py:49-51, :85 -------------------------------------------------------------
  * loss[0] += -(1/B) * sum_b ( -0.5*|z_b|^2 - 0.5*D*log(2 pi) + ld[b] )   (caller zero-fills loss)            */

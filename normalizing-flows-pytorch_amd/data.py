@@ -127,16 +127,35 @@ DS_WALK = 155                   # bound of the cycle walk: (3/4)^155 < 2^-64 (NF
 DS_KEY = 0x510e527f             # key constant that sets the permutation's Philox stream apart (NF_DS_KEY)
 
 
-def _philox_word0(c0, c1, c2, c3, k0, k1):
-    """word 0 of Philox4x32-10 (csrc/nf_philox.h) on uint64 arrays / scalars holding 32-bit words"""
+DQ_KEY = 0x9b05688c             # key constant of the dequantisation noise's Philox stream (NF_DQ_KEY)
+
+
+def _philox_words(c0, c1, c2, c3, k0, k1):
+    """the four words of Philox4x32-10 (csrc/nf_philox.h) on uint64 arrays / scalars holding 32-bit words"""
     M0, M1, W0, W1, m32 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), 0x9E3779B9, 0xBB67AE85, np.uint64(0xFFFFFFFF)
-    c0 = np.asarray(c0, dtype=np.uint64)
-    c1, c2, c3 = (np.broadcast_to(np.asarray(c, dtype=np.uint64), c0.shape) for c in (c1, c2, c3))
+    shape = np.broadcast(*(np.asarray(c) for c in (c0, c1, c2, c3))).shape
+    c0, c1, c2, c3 = (np.broadcast_to(np.asarray(c, dtype=np.uint64), shape) for c in (c0, c1, c2, c3))
     for r in range(10):
         p0, p1 = M0 * c0, M1 * c2
         ka, kb = np.uint64((k0 + r * W0) & 0xFFFFFFFF), np.uint64((k1 + r * W1) & 0xFFFFFFFF)
         c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ ka, p1 & m32, (p0 >> np.uint64(32)) ^ c3 ^ kb, p0 & m32
-    return c0
+    return c0, c1, c2, c3
+
+
+def _philox_word0(c0, c1, c2, c3, k0, k1):
+    """word 0 of Philox4x32-10 (csrc/nf_philox.h) on uint64 arrays / scalars holding 32-bit words"""
+    return _philox_words(c0, c1, c2, c3, k0, k1)[0]
+
+
+def dequant_words(seed, step, idx, n_bytes):
+    """the 32-bit noise words of the dequantising gather (csrc/dataset.hip, the DQ arm), uint32 of shape ``idx.shape + (n_bytes, )``:
+    byte b of data-set sample idx at device step ``step`` gets word b & 3 of Philox4x32-10(counter (b >> 2, idx, step lo, step hi),
+    key (seed lo, seed hi ^ DQ_KEY)); its top 15 bits are the noise below the byte.  ``seed`` as DeviceDataset stores it."""
+    seed, step, n_bytes = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, int(n_bytes)
+    idx = np.asarray(idx, dtype=np.int64)
+    quads = np.arange((n_bytes + 3) // 4, dtype=np.uint64)
+    w = _philox_words(quads, idx.astype(np.uint64)[..., None], step & 0xFFFFFFFF, step >> 32, seed & 0xFFFFFFFF, (seed >> 32) ^ DQ_KEY)
+    return np.stack(w, axis=-1).reshape(idx.shape + (-1, ))[..., :n_bytes].astype(np.uint32)
 
 
 def dataset_perm(seed, epoch, pos, N, rounds=DS_ROUNDS):
@@ -192,9 +211,17 @@ class DeviceDataset:
                 (the rank is not folded into the seed).  N <= world * batch is refused.
     Order       ``shuffle``: index = dataset_perm(seed, pass, position), evaluated in the gather kernel -- no index array, no reshuffle
                 launch (the reference: np.random.shuffle per pass); otherwise the identity.
-    ``device``  None builds a host-only object: ``indices`` / ``host_batch`` work, ``next()`` does not."""
+    ``device``  None builds a host-only object: ``indices`` / ``host_batch`` work, ``next()`` does not.
+    ``dequantize``  images only, off by default (the reference feeds uint8 / 255, dataset.py:120): out = (v + u) / 256 with 15 bits of
+                uniform noise u drawn in the gather kernel -- ((v * 2^15 + (w >> 17)) + 0.5) * 2^-23, w = dequant_words(seed, step, index,
+                bytes): strictly inside (0, 1), floor(256 x) == v, a pure function of (seed, step, sample, byte), so a captured step draws
+                fresh noise on every replay and ``host_batch(step)`` restates it bit for bit.  The pad ring stays 0.
+    ``sweep``   the schedule of a held-out score (FlowTrainer.evaluate): steps_per_epoch = ceil(N / (world * batch)), every sample is
+                served exactly once per pass; a position >= N is served sample N - 1 and is not valid (``valid(step)`` counts the real
+                rows).  N <= world * batch is allowed.  ``sweep_view()`` builds such a set over the device copy of this one."""
 
-    def __init__(self, source, batch, pad=0, seed=0, shuffle=True, device='cuda', rank=None, world=None):
+    def __init__(self, source, batch, pad=0, seed=0, shuffle=True, device='cuda', rank=None, world=None, dequantize=False, sweep=False,
+                 _share=None):
         arr = source.detach().cpu().numpy() if isinstance(source, torch.Tensor) else np.asarray(source)
         if arr.dtype == np.uint8 and arr.ndim in (3, 4):
             arr = arr.reshape(arr.shape + (1, )) if arr.ndim == 3 else arr
@@ -220,10 +247,18 @@ class DeviceDataset:
         self.stride, self.offset = self.world * self.batch, self.rank * self.batch
         if self.n >= 1 << 31:
             raise ValueError('DeviceDataset holds fewer than 2^31 samples')
-        if self.n <= self.stride:
-            raise ValueError('a data set of %d samples serves no batch of %d x %d: the loader needs N > world * batch (dataset.py:113)'
-                             % (self.n, self.world, self.batch))
-        self.steps_per_epoch = (self.n - 1) // self.stride
+        self.dequantize, self.sweep = bool(dequantize), bool(sweep)
+        if self.dequantize and not self.image:
+            raise ValueError('dequantize=True is for uint8 images: float32 rows hold no quantisation step to fill')
+        if self.sweep:
+            if self.stride >= 1 << 31:
+                raise ValueError('DeviceDataset(sweep=True): world * batch must stay below 2^31')
+            self.steps_per_epoch = -(-self.n // self.stride)
+        else:
+            if self.n <= self.stride:
+                raise ValueError('a data set of %d samples serves no batch of %d x %d: the loader needs N > world * batch (dataset.py:113)'
+                                 % (self.n, self.world, self.batch))
+            self.steps_per_epoch = (self.n - 1) // self.stride
         self.seed, self.shuffle = int(seed) & 0x7FFFFFFFFFFFFFFF, bool(shuffle)
         if self.image:
             _, H, W, C = arr.shape
@@ -231,10 +266,12 @@ class DeviceDataset:
         else:
             self.dims, self.dtype = (int(arr.shape[1]), ), '%dd' % arr.shape[1]
         self.data = self.out = self.step = self.last_indices = None
+        if _share is not None:                               # sweep_view(): the parent's device copy, no second upload
+            device = _share.device
         if device is not None:
             from . import _native as N
             self._N = N
-            self.data = torch.from_numpy(self.host).to(device)
+            self.data = _share if _share is not None else torch.from_numpy(self.host).to(device)
             self.out = torch.empty((self.batch, ) + self.dims, dtype=torch.float32, device=device)
             self.step = torch.zeros(1, dtype=torch.int64, device=device)
             self.last_indices = torch.zeros(self.batch, dtype=torch.int64, device=device)
@@ -253,29 +290,72 @@ class DeviceDataset:
         with np.load(path) as f:
             return cls(f[key], batch, **kw)
 
-    def next(self):
+    def sweep_view(self, batch=None, dequantize=None, shuffle=False):
+        """a sweep-schedule data set over the SAME device copy (no second upload) with its own step counter, batch tensor and -- by
+        default -- the identity order: what FlowTrainer.evaluate takes.  ``batch`` / ``dequantize`` default to this set's."""
+        return DeviceDataset(self.host, self.batch if batch is None else batch, pad=self.pad, seed=self.seed, shuffle=shuffle, device=None,
+                             rank=self.rank, world=self.world, dequantize=self.dequantize if dequantize is None else dequantize,
+                             sweep=True, _share=self.data)
+
+    def gather(self):
+        """one launch: this rank's batch of the step in device memory -> ``out`` (the step stays; ``advance()`` moves it on)"""
         if self.data is None:
             raise RuntimeError('this DeviceDataset was built with device=None: it has no device copy to gather from')
         N, a = self._N, (self.n, ) + (self.host.shape[1:] if self.image else (self.host.shape[1], ))
-        tail = (self.batch, self.stride, self.offset, self.steps_per_epoch, self.seed, int(self.shuffle), self.step.data_ptr(),
-                self.last_indices.data_ptr(), N.stream())
-        if self.image:
-            N.call('nf_dataset_gather_u8', self.data.data_ptr(), self.out.data_ptr(), a[0], a[1], a[2], a[3], self.pad, *tail)
+        head = (self.batch, self.stride, self.offset, self.steps_per_epoch, self.seed, int(self.shuffle))
+        tail = (self.step.data_ptr(), self.last_indices.data_ptr(), N.stream())
+        extra = self.dequantize or self.sweep
+        if self.image and extra:
+            N.call('nf_dataset_gather_u8_x', self.data.data_ptr(), self.out.data_ptr(), a[0], a[1], a[2], a[3], self.pad, *head,
+                   int(self.dequantize), int(self.sweep), *tail)
+        elif self.image:
+            N.call('nf_dataset_gather_u8', self.data.data_ptr(), self.out.data_ptr(), a[0], a[1], a[2], a[3], self.pad, *head, *tail)
+        elif extra:
+            N.call('nf_dataset_gather_f32_x', self.data.data_ptr(), self.out.data_ptr(), a[0], a[1], *head, int(self.sweep), *tail)
         else:
-            N.call('nf_dataset_gather_f32', self.data.data_ptr(), self.out.data_ptr(), a[0], a[1], *tail)
-        N.call('nf_sample_advance', self.step.data_ptr(), N.stream())
+            N.call('nf_dataset_gather_f32', self.data.data_ptr(), self.out.data_ptr(), a[0], a[1], *head, *tail)
         return self.out
 
-    def indices(self, step):
-        """(batch, ) int64: the samples this rank is served at ``step`` (numpy; what the kernel writes to ``last_indices``)"""
+    def advance(self):
+        self._N.call('nf_sample_advance', self.step.data_ptr(), self._N.stream())
+
+    def next(self):
+        out = self.gather()
+        self.advance()
+        return out
+
+    def _positions(self, step):
         epoch, k = divmod(int(step), self.steps_per_epoch)
-        pos = k * self.stride + self.offset + np.arange(self.batch, dtype=np.int64)
-        return dataset_perm(self.seed, epoch, pos, self.n) if self.shuffle else pos
+        return epoch, k * self.stride + self.offset + np.arange(self.batch, dtype=np.int64)
+
+    def valid(self, step):
+        """the number of real rows in the batch of ``step``: ``batch`` on the loader's schedule, fewer in a sweep's last steps"""
+        if not self.sweep:
+            return self.batch
+        return int(min(max(self.n - self._positions(step)[1][0], 0), self.batch))
+
+    def indices(self, step):
+        """(batch, ) int64: the samples this rank is served at ``step`` (numpy; what the kernel writes to ``last_indices``); a sweep's
+        positions beyond the set are clamped to sample N - 1"""
+        epoch, pos = self._positions(step)
+        if not self.sweep:
+            return dataset_perm(self.seed, epoch, pos, self.n) if self.shuffle else pos
+        idx, ok = np.full(self.batch, self.n - 1, dtype=np.int64), pos < self.n
+        idx[ok] = dataset_perm(self.seed, epoch, pos[ok], self.n) if self.shuffle else pos[ok]
+        return idx
 
     def host_batch(self, step):
-        """the batch of ``step`` as the reference builds it on the host (dataset.py:116-125), a float32 torch tensor"""
-        rows = self.host[self.indices(step)]
+        """the batch of ``step`` as the reference builds it on the host (dataset.py:116-125), a float32 torch tensor; with
+        ``dequantize`` the kernel's noise restated in numpy (every operation is exact in float32)"""
+        idx = self.indices(step)
+        rows = self.host[idx]
         if not self.image:
             return torch.from_numpy(rows)
-        x, p = np.transpose(rows.astype('float32') / 255.0, (0, 3, 1, 2)), self.pad
+        if self.dequantize:
+            w = dequant_words(self.seed, step, idx, rows[0].size).reshape(rows.shape)
+            q = (rows.astype(np.uint32) << np.uint32(15)) | (w >> np.uint32(17))
+            x = (q.astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -23)
+        else:
+            x = rows.astype('float32') / 255.0
+        x, p = np.transpose(x, (0, 3, 1, 2)), self.pad
         return torch.from_numpy(np.ascontiguousarray(np.pad(x, ((0, 0), (0, 0), (p, p), (p, p))).astype(np.float32)))

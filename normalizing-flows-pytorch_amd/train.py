@@ -635,6 +635,89 @@ class FlowTrainer:
         return standard_normal_logprob(z) + ld
 
     @torch.no_grad()
+    def evaluate(self, dataset, graph=False, keep_rows=False):
+        """held-out score of the model over a whole device-resident set: main.py:121-127 taken over every sample exactly once.
+
+        ``dataset``  a data.DeviceDataset on the SWEEP schedule (``train_set.sweep_view()`` or ``DeviceDataset(..., sweep=True)``).
+        Returns {'n', 'nll' (nats per sample, -sum log p / n), 'stderr' (of nll, from the second moment), 'bits_per_dim'} and, for a
+        dequantised image set, 'bits_per_dim_pixel' = bits_per_dim + 8: the density is that of pixel / 256 in [0, 1), 8 bits per
+        dimension away from the density of the 0..255 pixel.  D is the size of what the model sees, so with a pad ring it is the PADDED
+        size throughout (the ring's constant zeros are scored as data, as the reference's padded MNIST is).
+        The model goes to eval() under no_grad; the accumulator and the set's step counter are zeroed, then every step launches
+        gather -> net(y) -> nf_logp_accumulate -> advance with NO host synchronisation between batches; the three float64 sums are read
+        once at the end (after one all-reduce under an initialised process group, where each rank sweeps its own positions).  Zeroing
+        the step makes two calls on the same weights return the same bits, dequantisation noise included.
+        ``keep_rows``  also returns 'rows': the float64 log p of this rank's valid samples in the order served (the data-set order for
+        the identity order at world size 1).
+        ``graph``  one step's launches are captured once and replayed for every step; a capture that raises warns and the sweep runs on
+        eager launches.  The model is left in eval(): the next train_on_batch() puts it back, captured or not."""
+        from . import _native as N
+        from .models import Ffjord
+        if not getattr(dataset, 'sweep', False):
+            raise ValueError('FlowTrainer.evaluate scores every sample exactly once: it takes a sweep-schedule data set, and this one '
+                             'follows the loader (which drops the tail) -- pass dataset.sweep_view()')
+        if isinstance(self.net, Ffjord):
+            raise NotImplementedError('FlowTrainer.evaluate does not serve FFJORD (float64 states, adaptive integration)')
+        if dataset.data is None:
+            raise RuntimeError('this DeviceDataset was built with device=None: it has no device copy to gather from')
+        self.net.eval()
+        dev = dataset.data.device
+        S, B, D = dataset.steps_per_epoch, dataset.batch, 1
+        for d_ in dataset.dims:
+            D *= int(d_)
+        acc = torch.zeros(3, dtype=torch.float64, device=dev)
+        row = torch.empty(B, dtype=torch.float64, device=dev)
+        rows_all = torch.empty(S * B, dtype=torch.float64, device=dev) if keep_rows else None
+
+        def one_step():
+            y = dataset.gather()
+            z, ld = self.net(y)
+            if z.dtype != torch.float32 or ld.dtype != torch.float32:
+                raise NotImplementedError('FlowTrainer.evaluate takes float32 models, got z %s, ld %s' % (z.dtype, ld.dtype))
+            z, ld = z.contiguous(), ld.contiguous()
+            N.call('nf_logp_accumulate', N.ptr(z), N.ptr(ld), row.data_ptr(), None, None if rows_all is None else rows_all.data_ptr(),
+                   acc.data_ptr(), B, D, dataset.n, dataset.stride, dataset.offset, dataset.step.data_ptr(), N.stream())
+            dataset.advance()                           # AFTER the fold has read the step
+
+        g = None
+        if graph:
+            try:
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):           # one eager step on the side stream (capture etiquette); its sums are zeroed below
+                    one_step()
+                torch.cuda.current_stream().wait_stream(side)
+                torch.cuda.synchronize()
+                g = self._graph_factory()
+                g.capture(one_step)
+            except Exception as e:
+                import warnings
+                warnings.warn('hipGraph capture of the evaluation step failed (%s: %s); continuing with eager launches' % (type(e).__name__, e))
+                g = None
+                torch.cuda.synchronize()
+        acc.zero_()
+        dataset.step.zero_()
+        for _ in range(S):
+            if g is not None:
+                g.replay()
+            else:
+                one_step()
+        import torch.distributed as _d
+        if _d.is_available() and _d.is_initialized():
+            _d.all_reduce(acc, op=_d.ReduceOp.SUM, group=self.bucket.group)
+        s1, s2, n = (float(v) for v in acc.cpu())       # the one read of the sweep
+        n_i = int(round(n))
+        nll = -s1 / n
+        var = max(s2 / n - (s1 / n) ** 2, 0.0) * (n / (n - 1.0)) if n_i > 1 else 0.0
+        res = {'n': n_i, 'nll': nll, 'stderr': math.sqrt(var / n), 'bits_per_dim': bits_per_dim(nll, dataset.dims)}
+        if dataset.image and dataset.dequantize:
+            res['bits_per_dim_pixel'] = res['bits_per_dim'] + 8.0
+        if keep_rows:
+            all_rows = rows_all.cpu().reshape(S, B)
+            res['rows'] = torch.cat([all_rows[s, :dataset.valid(s)] for s in range(S)])
+        return res
+
+    @torch.no_grad()
     def sample_y(self, n, dims, generator=None):
         self.net.eval()
         dev = next(self.net.parameters()).device
