@@ -1223,6 +1223,53 @@ int nf_dataset_gather_f32_x(const float* data, float* out, int64_t N, int64_t D,
 int nf_logp_accumulate(const float* z, const float* ld, double* logp_row, float* logp_f32, double* rows_all, double* acc, int64_t B,
                        int64_t D, int64_t N, int64_t stride, int64_t offset, const int64_t* step, nf_stream_t stream);
 
+/* ---- what Model.report computes before matplotlib sees it (csrc/report.hip)  main.py:135-284, common/utils.py:12-83 ---------------
+ * uint8 RGB panels (no axes, ticks, titles or colour bars) built on the device.  Every number that decides a pixel or a table index is a
+ * double computed without multiply-add contraction, so the numpy restatements in report.py (*_host) give the same bits.  Each entry
+ * point checks its arguments on the host and returns NF_E_BADARG before any launch.                                                  */
+#define NF_CMAP_INFERNO 0   /* image_plot's map    common/utils.py:47 */
+#define NF_CMAP_JET 1       /* scatter_plot's map  common/utils.py:19, :27 */
+/* the points of the density map, main.py:199-206: y (map_size^2, 2) float32, row-major over (i, j),
+ *   y[i, j] = ((j + 0.5) / map_size * 2.0 - 1.0, (i + 0.5) / map_size * -2.0 + 1.0)  in double, stored as float32.
+ * NF_E_BADARG: y NULL, map_size < 1 or > 16384.                                                                                      */
+int nf_report_grid(float* y, int map_size, nf_stream_t stream);
+/* range2 (DEVICE double[2]) = {min, max} over the FINITE values of v (n floats); {0, 1} when there is none.  Three launches, no host
+ * synchronisation: what matplotlib's scatter(c=...) autoscales to (common/utils.py:19), for the launches that follow to read.
+ * NF_E_BADARG: v or range2 NULL, n < 1.                                                                                              */
+int nf_report_minmax(const float* v, int64_t n, double* range2, nf_stream_t stream);
+/* value -> colour (common/utils.py:19, :59: cmap(Normalize(lo, hi)(p), bytes=True)).  p = is_log ? (float)exp((double)v) : v, stored to
+ * p_out (n floats, may be NULL, may be v) -- main.py:129-133's exp.  rgb (n, 3) uint8 (may be NULL when p_out is not) is a function of
+ * the stored float32 p alone: x = ((double)p - lo) / (hi - lo) with (lo, hi) = range_dev[0..1] (device) when range_dev is given, else
+ * (vmin, vmax); table index 0 if x < 0 or hi == lo, 255 if x >= 1, else floor(x * 256); a NaN p gives (0, 0, 0).
+ * NF_E_BADARG: v NULL, n < 1, p_out and rgb both NULL, cmap not an NF_CMAP_* id, is_log outside {0, 1}, a non-finite vmin / vmax
+ * without range_dev.                                                                                                                 */
+int nf_report_colorize(const float* v, int64_t n, int is_log, const double* range_dev, double vmin, double vmax, int cmap, float* p_out,
+                       uint8_t* rgb, nf_stream_t stream);
+/* host only: out768 (HOST, 256 x 3 uint8) = the table of map `cmap`, the bytes the kernels index (csrc/nf_cmaps.h, written by
+ * tools/make_cmaps.py from matplotlib's colormaps[name](np.arange(256), bytes=True)[:, :3]).  NF_E_BADARG: NULL, unknown id.         */
+int nf_report_cmap(int cmap, uint8_t* out768);
+/* a scatter panel (common/utils.py:12-43, data area only): n points (n, D) float32, D in {2, 3}, with colours rgb_pt (n, 3) uint8, on
+ * an S x S canvas over [-1, 1]^2 with a white background, rgb_out (S, S, 3) uint8.  keys (S * S, uint64): scratch.
+ *   D = 3: (u, v, depth) = view9 (HOST, row-major 3 x 3 double; report.view_matrix gives elev 10, azim -80, orthographic:
+ *          common/utils.py:24) times the point, each row as (m0 x + m1 y) + m2 z.  D = 2: (u, v) = (x, y), depth = 0; view9 is ignored.
+ *   centre pixel cx = floor((u + 1) * 0.5 * S), cy = floor((1 - v) * 0.5 * S); the point covers the canvas pixels with
+ *   dx^2 + dy^2 <= radius^2.  Points with a non-finite coordinate and points whose disc lies wholly outside are skipped.
+ *   A pixel shows the point with the largest key (depth_q << 32) | (index + 1), depth_q = floor(clamp((depth + 2) / 4, 0, 1) * 1048575):
+ *   in 2-D the later point paints over the earlier (matplotlib's order), in 3-D the nearer wins and ties go to the later index.
+ * Three launches: clear keys; one thread per point, atomicMax over its disc; resolve.  The image does not depend on scheduling.
+ * NF_E_BADARG: keys or rgb_out NULL, n < 0 or >= 2^31, pts or rgb_pt NULL with n > 0, D outside {2, 3}, view9 NULL with D = 3,
+ * S < 1 or > 4096, radius < 0 or > 8.  n = 0 gives a white canvas.                                                                    */
+int nf_report_scatter(const float* pts, const uint8_t* rgb_pt, int64_t n, int D, const double* view9, int S, int radius,
+                      unsigned long long* keys, uint8_t* rgb_out, nf_stream_t stream);
+/* main.py:258-263 and common/utils.py:76-78 in one pass: torchvision's make_grid(clamp(x, 0, 1), nrow, padding, pad_value), permute to
+ * HWC and (image * 255.0).astype('uint8').  x (n, C, H, W) float32, C in {1, 3} (one channel is replicated to three); xmaps = min(nrow, n),
+ * ymaps = ceil(n / xmaps); out ((H + padding) * ymaps + padding, (W + padding) * xmaps + padding, 3) uint8.  A pixel is
+ * (uint8)(clamp(x, 0, 1) * 255.0f), NaN -> 0; borders and empty cells hold pad_value through the same conversion.  n = 1 follows the same
+ * formula (torchvision returns the bare image there).
+ * NF_E_BADARG: x or out NULL, n < 1, C outside {1, 3}, H, W, nrow < 1, padding < 0, an output side of 2^31 or more.                    */
+int nf_report_image_grid(const float* x, int64_t n, int C, int H, int W, int nrow, int padding, float pad_value, uint8_t* out,
+                         nf_stream_t stream);
+
 /* ---- NLL of the training harness  main.py:49-51, :85 -------------------------------------------------------------
  * loss[0] += -(1/B) * sum_b ( -0.5*|z_b|^2 - 0.5*D*log(2 pi) + ld[b] )   (caller zero-fills loss)            */
 int nf_nll_loss(const float* z, const float* ld, float* loss, int64_t B, int64_t D, nf_stream_t stream);

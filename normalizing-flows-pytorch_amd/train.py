@@ -718,6 +718,27 @@ class FlowTrainer:
         return res
 
     @torch.no_grad()
+    def report(self, y_data, n_samples=None, graph=False, generator=None, map_size=256, canvas=512, radius=2):
+        """what Model.report computes before matplotlib, tensorboard and the jpg writer take over (main.py:135-284), as numpy arrays
+        from ONE host read: everything is queued on the current stream, copied to pinned memory, and synchronised once.  The panels
+        (``*_rgb``, ``*_grid``) are uint8 HWC images rasterised on the device (csrc/report.hip) -- the data area alone, no axes, ticks,
+        titles or colour bars -- that PIL.Image.fromarray or SummaryWriter.add_image(..., dataformats='HWC') take as they are.
+        By the case of main.py:142-147:
+          (n, 2)   'z', 'pz', 'y_sample', 'py_sample' (float32); 'z_rgb', 'y_rgb' (canvas, canvas, 3): jet over the finite range of pz /
+                   py_sample; 'y_data_rgb': the batch in one colour (jet[0]); 'py_map' (map_size, map_size) float32: the density of the
+                   grid of main.py:199-206 through the whole flow; 'py_map_rgb': inferno over (0, 1), image_plot's defaults
+          (n, 3)   the same without the map; the scatters are seen through report.view_matrix() (elev 10, azim -80)
+          images   'data_grid', 'sample_grid': make_grid(clamp(., 0, 1), nrow=8, pad_value=1) as uint8 HWC, the second over 'y_sample',
+                   the first 64 of the samples drawn
+        ``n_samples``  default: the reference's max(100, n) for vectors, max(64, n) for images.  ``generator``: of the latent draw.
+        ``graph``      (2-D) the chain grid -> net(y) -> log p -> colours is captured once per map_size and replayed by later calls: its
+                       input is a constant.  A capture that raises warns and the call continues eagerly, as in ``evaluate``.
+        The model is left in eval(), like log_py(): the next train_on_batch() puts it back, captured or not."""
+        from . import report as _report
+        return _report.report(self, y_data, n_samples=n_samples, graph=graph, generator=generator, map_size=map_size, canvas=canvas,
+                              radius=radius)
+
+    @torch.no_grad()
     def sample_y(self, n, dims, generator=None):
         self.net.eval()
         dev = next(self.net.parameters()).device
