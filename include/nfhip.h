@@ -1296,6 +1296,42 @@ int nf_rmsprop_step(float* param, const float* grad, float* square_avg, int* ste
  * pos is the schedule's own counter (restarted by a checkpoint load), not Adam's bias-correction step.                  */
 int nf_lr_step_decay(float* lr, const double* base_lr, int* pos, int decay_steps, double decay_ratio, nf_stream_t stream);
 
+/* ---- the guarded step: clipping, non-finite skip and averaged weights inside the train step (main.py:78-92) ---------------------
+ * The control block lives in device memory (zero it once); a captured hipGraph replays every decision without a host read.          */
+#define NF_GUARD_MAX_PARTIALS 1024        /* doubles in the partials slab nf_grad_guard is handed                                      */
+typedef struct nf_guard_ctl {
+    float grad_norm;                      /* 2-norm of the flat gradient of the last call                                              */
+    float clip_scale;                     /* min(1, max_norm / (grad_norm + 1e-6)); 1 with max_norm <= 0                               */
+    int skip;                             /* 1: the last gradient was not finite and skip_nonfinite was set -- the step does nothing   */
+    int skipped;                          /* running count of such steps                                                               */
+    int ema_count;                        /* running count of steps taken: 1 makes the guarded step COPY the parameters into ema       */
+    int reserved_[3];
+} nf_guard_ctl;
+/* torch.nn.utils.clip_grad_norm_(params, max_norm) up to (not including) the multiplication, and the `if not isfinite` a host loop
+ * puts between backward and optimizer.step() (main.py:86-89), over the flat float32 gradient grad[0 .. n): two launches.  The first
+ * writes one float64 sum of squares per workgroup into partials (NF_GUARD_MAX_PARTIALS doubles, no atomics); the second, one
+ * workgroup behind the kernel boundary, adds them in index order and fills ctl: grad_norm, clip_scale, skip = skip_nonfinite && the
+ * sum is not finite.  With skip = 0 it also ticks step[0] (the optimizer's counter, what nf_adam_step's own tick does; may be NULL)
+ * and ctl->ema_count; with skip = 1 it ticks ctl->skipped alone.  The same bits on every run for a given n and alignment of grad.
+ * The gradient is left as it is: the guarded steps apply clip_scale.
+ * NF_E_BADARG: n < 0, ctl NULL, grad or partials NULL with n > 0.  n = 0: nothing is launched.                                       */
+int nf_grad_guard(const float* grad, int64_t n, float max_norm, int skip_nonfinite, double* partials, nf_guard_ctl* ctl, int* step,
+                  nf_stream_t stream);
+/* torch.optim.Adam.step / torch.optim.RMSprop.step (main.py:56-64, :89) after nf_grad_guard: nf_adam_step's / nf_rmsprop_step's
+ * arithmetic with grad_scale = ctl->clip_scale (applied before weight decay, the order of clip-then-step), NO tick of step (the guard
+ * did that), and nothing read or written when ctl->skip is set.  ema (may be NULL): the averaged weights, updated in the same pass
+ * from the new parameter: ema = p when ctl->ema_count == 1, else ema_decay * ema + (1 - ema_decay) * p.  One launch.
+ * NF_E_BADARG: n < 0, ctl NULL, any other pointer but ema NULL with n > 0.  n = 0: nothing is launched.                              */
+int nf_adam_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const int* step, const float* lr,
+                         float beta1, float beta2, float eps, float weight_decay, const nf_guard_ctl* ctl, float* ema, float ema_decay,
+                         int64_t n, nf_stream_t stream);
+int nf_rmsprop_step_guarded(float* param, const float* grad, float* square_avg, const float* lr, float alpha, float eps,
+                            float weight_decay, const nf_guard_ctl* ctl, float* ema, float ema_decay, int64_t n, nf_stream_t stream);
+/* a[0 .. n) <-> b[0 .. n) in place, one launch: the averaged weights into the parameters for evaluation (main.py:121-124 on the
+ * average) and back, without a temporary and without moving a pointer a captured graph holds.
+ * NF_E_BADARG: n < 0, a or b NULL with n > 0, overlapping ranges (a == b is a no-op).                                                */
+int nf_swap_f32(float* a, float* b, int64_t n, nf_stream_t stream);
+
 /* dst_k[0:n_k] = src_k[0:n_k] for up to NF_COPY_MAX tensors in one launch (gradient gather into the flat bucket)   */
 #define NF_COPY_MAX 128
 typedef struct nf_copy_desc {

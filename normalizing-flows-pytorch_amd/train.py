@@ -35,6 +35,15 @@ def bits_per_dim(loss, dims):
     return float(loss) / (D * math.log(2.0))
 
 
+def _check_ema_decay(d):
+    if d is None:
+        return None
+    d = float(d)
+    if not 0.0 <= d < 1.0:
+        raise ValueError('ema_decay must lie in [0, 1), got %r' % (d, ))
+    return d
+
+
 class _FlatOptimizer:
     """What FlatAdam and FlatRMSprop share: ONE fused HIP launch over the flat parameter / gradient buffers of a GradBucket, with
     ``lr`` and the step counter on the device, so that a captured hipGraph keeps working when the rate changes (``set_lr``).
@@ -43,12 +52,18 @@ class _FlatOptimizer:
     in front of the optimizer launch and therefore part of a captured step): optimizer step t = 1, 2, ... since construction or the
     last checkpoint load runs at ``base_lr * decay_ratio ** ((t - 1) // decay_steps)``, the rate StepLR gives when scheduler.step()
     follows optim.step() (main.py:89-90).  ``sched_pos`` counts those steps; it is NOT ``step_count``, which a checkpoint carries on
-    (Adam's bias correction) while the reference's schedule restarts at every load.  ``lr`` holds the rate in use."""
+    (Adam's bias correction) while the reference's schedule restarts at every load.  ``lr`` holds the rate in use.
+
+    ``max_grad_norm`` / ``skip_nonfinite`` / ``ema_decay`` (all off by default: the launches are then the plain ones) turn the
+    optimizer launch into nf_grad_guard + the guarded step (csrc/optim_guard.hip): the gradient's 2-norm in float64,
+    torch's clip scale and a skip flag in a device control block, the step reading both from there, the average ``ema`` updated in the
+    same pass.  ``step_count`` does not advance on a skipped step; ``sched_pos`` does.  ``guard_state()`` reads the block.  Neither the
+    average nor the skip count is torch optimizer state: ``torch_state_dict()`` does not carry them."""
 
     KIND = None                     # 'Adam' / 'RMSprop': the torch.optim class whose state_dict format torch_state_dict() speaks
     MOMENTS = ()                    # names of the per-parameter moment buffers, as torch.optim names them
 
-    def _init_common(self, bucket, lr, decay_steps, decay_ratio):
+    def _init_common(self, bucket, lr, decay_steps, decay_ratio, max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
         if bucket.flat_params is None:
             raise ValueError('%s needs GradBucket(..., flatten_params=True)' % type(self).__name__)
         from . import _native as N
@@ -67,6 +82,44 @@ class _FlatOptimizer:
                 raise ValueError('decay_steps must be a positive number of optimizer steps, got %r' % (decay_steps, ))
             self.base_lr = torch.full((1, ), float(lr), dtype=torch.float64, device=dev)
             self.sched_pos = torch.zeros(1, dtype=torch.int32, device=dev)
+        # the guarded step (csrc/optim_guard.hip).  With all three off none of the tensors below exists and _launch() issues the
+        # plain nf_adam_step / nf_rmsprop_step; with any of them on it is nf_grad_guard followed by the guarded step
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.ema_decay = _check_ema_decay(ema_decay)
+        self.guarded = self.max_grad_norm is not None or self.skip_nonfinite or self.ema_decay is not None
+        self.guard_ctl = self._partials = self.ema = None
+        if self.guarded:
+            # nf_guard_ctl: float grad_norm, clip_scale; int skip, skipped, ema_count, reserved[3] -- allocated once, a captured step
+            # replays on it
+            self.guard_ctl = torch.zeros(8, dtype=torch.int32, device=dev)
+            self._partials = torch.zeros(N.header_constant('NF_GUARD_MAX_PARTIALS'), dtype=torch.float64, device=dev)
+            if self.ema_decay is not None:
+                self.ema = bucket.flat_params.detach().clone()      # (the first step that is taken overwrites it with the parameters)
+
+    def _guard(self):
+        """nf_grad_guard over the bucket: norm, clip scale and skip flag into the control block; ticks step_count unless it skips"""
+        N, b = self._N, self.bucket
+        N.call('nf_grad_guard', N.ptr(b.flat), b.numel, 0.0 if self.max_grad_norm is None else self.max_grad_norm,
+               1 if self.skip_nonfinite else 0, N.ptr(self._partials, (torch.float64, )), N.ptr(self.guard_ctl),
+               N.ptr(self.step_count), N.stream())
+
+    def guard_state(self):
+        """{'grad_norm', 'clip_scale'} of the last step, {'skipped', 'steps'}: the steps refused for a non-finite gradient and the steps
+        taken since construction (a checkpoint load restores the first and leaves the second at 1 or more).  ONE host read."""
+        if not self.guarded:
+            raise ValueError('%s was built without max_grad_norm / skip_nonfinite / ema_decay: there is no guard state' % type(self).__name__)
+        w = self.guard_ctl.cpu()
+        f = w[:2].view(torch.float32)
+        return {'grad_norm': float(f[0]), 'clip_scale': float(f[1]), 'skipped': int(w[3]), 'steps': int(w[4])}
+
+    def swap_ema_(self):
+        """parameters <-> averaged weights, in place (nf_swap_f32): no temporary, no pointer moves"""
+        N, b = self._N, self.bucket
+        if self.ema is None:
+            raise ValueError('%s was built without ema_decay' % type(self).__name__)
+        self._check_homed()
+        N.call('nf_swap_f32', N.ptr(b.flat_params), N.ptr(self.ema), b.numel, N.stream())
 
     def set_lr(self, lr):
         """the rate of a trainer without a schedule, the BASE rate of one with a schedule"""
@@ -206,15 +259,22 @@ class FlatAdam(_FlatOptimizer):
 
     KIND, MOMENTS = 'Adam', ('exp_avg', 'exp_avg_sq')
 
-    def __init__(self, bucket, lr=1.0e-4, betas=(0.9, 0.999), eps=1.0e-8, weight_decay=0.0, decay_steps=None, decay_ratio=0.5):
+    def __init__(self, bucket, lr=1.0e-4, betas=(0.9, 0.999), eps=1.0e-8, weight_decay=0.0, decay_steps=None, decay_ratio=0.5,
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
-        self._init_common(bucket, lr, decay_steps, decay_ratio)
+        self._init_common(bucket, lr, decay_steps, decay_ratio, max_grad_norm, skip_nonfinite, ema_decay)
 
     def _hyper(self):
         return {'betas': (float(self.betas[0]), float(self.betas[1])), 'eps': self.eps, 'weight_decay': self.weight_decay}
 
     def _launch(self):
         N, b = self._N, self.bucket
+        if self.guarded:
+            self._guard()
+            N.call('nf_adam_step_guarded', N.ptr(b.flat_params), N.ptr(b.flat), N.ptr(self.exp_avg), N.ptr(self.exp_avg_sq),
+                   N.ptr(self.step_count), N.ptr(self.lr), self.betas[0], self.betas[1], self.eps, self.weight_decay,
+                   N.ptr(self.guard_ctl), N.ptr(self.ema), self.ema_decay or 0.0, b.numel, N.stream())
+            return
         N.call('nf_adam_step', N.ptr(b.flat_params), N.ptr(b.flat), N.ptr(self.exp_avg), N.ptr(self.exp_avg_sq),
                N.ptr(self.step_count), N.ptr(self.lr), self.betas[0], self.betas[1], self.eps, self.weight_decay, 1.0,
                b.numel, N.stream())
@@ -226,15 +286,21 @@ class FlatRMSprop(_FlatOptimizer):
 
     KIND, MOMENTS = 'RMSprop', ('square_avg', )
 
-    def __init__(self, bucket, lr=1.0e-2, alpha=0.99, eps=1.0e-8, weight_decay=0.0, decay_steps=None, decay_ratio=0.5):
+    def __init__(self, bucket, lr=1.0e-2, alpha=0.99, eps=1.0e-8, weight_decay=0.0, decay_steps=None, decay_ratio=0.5,
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
         self.alpha, self.eps, self.weight_decay = alpha, eps, weight_decay
-        self._init_common(bucket, lr, decay_steps, decay_ratio)
+        self._init_common(bucket, lr, decay_steps, decay_ratio, max_grad_norm, skip_nonfinite, ema_decay)
 
     def _hyper(self):
         return {'alpha': self.alpha, 'eps': self.eps, 'weight_decay': self.weight_decay}
 
     def _launch(self):
         N, b = self._N, self.bucket
+        if self.guarded:
+            self._guard()
+            N.call('nf_rmsprop_step_guarded', N.ptr(b.flat_params), N.ptr(b.flat), N.ptr(self.square_avg), N.ptr(self.lr), self.alpha,
+                   self.eps, self.weight_decay, N.ptr(self.guard_ctl), N.ptr(self.ema), self.ema_decay or 0.0, b.numel, N.stream())
+            return
         N.call('nf_rmsprop_step', N.ptr(b.flat_params), N.ptr(b.flat), N.ptr(self.square_avg), N.ptr(self.step_count),
                N.ptr(self.lr), self.alpha, self.eps, self.weight_decay, 1.0, b.numel, N.stream())
 
@@ -274,11 +340,41 @@ class _HipStepGraph:
         self.g.replay()
 
 
+class _EmaWeights:
+    """``with trainer.ema_weights():`` -- two in-place exchanges of parameters and average, the second one in ``__exit__``"""
+
+    def __init__(self, trainer):
+        self.trainer = trainer
+
+    def __enter__(self):
+        tr = self.trainer
+        if tr._in_ema:
+            raise RuntimeError('FlowTrainer.ema_weights() does not nest: the parameters already hold the averaged weights')
+        tr._swap_ema()
+        tr._in_ema = True
+        return tr
+
+    def __exit__(self, *exc):
+        self.trainer._swap_ema()
+        self.trainer._in_ema = False
+        return False
+
+
 class FlowTrainer:
     """Adam (lr 1e-4, betas (0.9, 0.999): configs/default.yaml:13-20) or RMSprop (``optimizer='rmsprop'``, main.py:56-59) on the
     NLL, gradients in one flat bucket.  ``decay_steps`` / ``decay_ratio``: the reference's StepLR (main.py:68-70, :90), on the device
     and inside the captured step with the fused optimizers, torch.optim.lr_scheduler.StepLR on the torch.optim path (CPU, or
     ``fused_adam=False``).  ``save_ckpt`` / ``load_ckpt`` speak the reference's checkpoint format (main.py:94-107).
+
+    Three options the reference's loop (main.py:78-92) does not have, all off by default -- the step is then what it always was:
+    ``max_grad_norm`` clips the global 2-norm of the (all-reduced) gradient as torch.nn.utils.clip_grad_norm_ does;
+    ``skip_nonfinite`` leaves parameters, moments, step count and average untouched when that norm is not finite (the schedule
+    position still advances); ``ema_decay`` keeps an exponential moving average of the parameters, copied from them at the first
+    step taken (after ActNorm's data-dependent initialisation) -- ``ema_weights()``, ``evaluate(ema=True)``, ``report(ema=True)``.
+    With the fused optimizers all three run on the device inside the (captured) step, without a host read (csrc/optim_guard.hip,
+    ``guard_state()``); on the torch.optim path they are clip_grad_norm_, a host isfinite check and _foreach_lerp_.  Known limit: a
+    non-finite FORWARD has written NaN into BatchNorm running statistics before the guard sees the gradient; running statistics
+    are not snapshotted, and ``guard_state()['skipped']`` rising is the signal to reload a checkpoint.
 
     ``graph=True`` captures zero-grad + forward + backward into one hipGraph and the optimizer step into a second one
     (the gradient all-reduce runs between the two replays; a single process captures both into ONE graph), after
@@ -289,10 +385,20 @@ class FlowTrainer:
 
     def __init__(self, net, lr=1.0e-4, betas=(0.9, 0.999), weight_decay=0.0, graph=False, warmup=3, process_group=None,
                  fused_adam=True, sampler=None, sync_stats=False, graph_factory=None, one_graph=None, optimizer='adam',
-                 decay_steps=None, decay_ratio=0.5):
+                 decay_steps=None, decay_ratio=0.5, max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
         if optimizer not in ('adam', 'rmsprop'):
             raise Exception('optimizer "%s" is currently not supported' % (optimizer, ))       # (the reference's words, main.py:66)
         self.net = net
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.ema_decay = _check_ema_decay(ema_decay)
+        guard_kw = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay)
+        self._guarded = self.max_grad_norm is not None or self.skip_nonfinite or self.ema_decay is not None
+        self._in_ema = False        # inside ``with trainer.ema_weights():`` the parameters hold the average
+        # the torch.optim path's guard state (host side; the fused optimizers keep theirs in the device control block)
+        self._ema = None            # one tensor per bucketed parameter
+        self._ema_count = self._skipped = 0
+        self._last_norm = None
         self.one_graph = (os.environ.get('NF_DP_ONE_GRAPH', '0') == '1') if one_graph is None else bool(one_graph)
         self._g_whole = False
         # parity mode: every batch statistic over the GLOBAL batch -- W-way data parallelism then reproduces
@@ -331,12 +437,18 @@ class FlowTrainer:
         if fused_adam:
             if optimizer == 'adam':
                 self.optim = FlatAdam(self.bucket, lr=lr, betas=betas, weight_decay=weight_decay, decay_steps=decay_steps,
-                                      decay_ratio=decay_ratio)
+                                      decay_ratio=decay_ratio, **guard_kw)
             else:
                 self.optim = FlatRMSprop(self.bucket, lr=lr, weight_decay=weight_decay, decay_steps=decay_steps,
-                                         decay_ratio=decay_ratio)
+                                         decay_ratio=decay_ratio, **guard_kw)
         else:
             capturable = self.graph and on_gpu
+            if capturable and self.skip_nonfinite:
+                raise ValueError('skip_nonfinite=True with a captured torch.optim optimizer (graph=True, fused_adam=False) would need a '
+                                 'host read between backward and the optimizer inside the hipGraph; train with the fused optimizers '
+                                 '(fused_adam=True) or without graph=True')
+            if self.ema_decay is not None:
+                self._ema = [p.detach().clone() for p in self.bucket.params]
             if capturable and decay_steps is not None:
                 # a captured framework optimizer reads a python-float rate once, at capture: the scheduler needs a device tensor to fill
                 lr = torch.tensor(float(lr), dtype=torch.float32, device=next(net.parameters()).device)
@@ -434,9 +546,65 @@ class FlowTrainer:
     def _optim_step(self):
         """one eager optimizer step.  The fused optimizers carry their schedule inside ``step()``; the torch.optim path's StepLR is
         host code and follows it here -- and every graph replay in train_on_batch, never inside a capture."""
-        self.optim.step()
+        self._optim_only()
         if self._sched is not None:
             self._sched.step()
+
+    def _optim_only(self):
+        """the optimizer's own step: what a capture records.  The fused optimizers carry clipping, the non-finite guard and the
+        average inside ``step()`` (csrc/optim_guard.hip); on the torch.optim path they take their host forms here:
+        clip_grad_norm_, an isfinite check of its norm that skips ``optim.step()`` (a host read: never under a real capture, the
+        constructor refuses that), and ``_foreach_lerp_`` for the average -- a copy at the first update that is taken."""
+        if self._fused or not self._guarded:
+            self.optim.step()
+            return
+        params = self.bucket.params
+        if self.max_grad_norm is not None:
+            norm = torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm)
+        else:
+            norm = torch.linalg.vector_norm(torch.stack(torch._foreach_norm([p.grad for p in params])))
+        self._last_norm = norm
+        if self.skip_nonfinite and not bool(torch.isfinite(norm)):
+            self._skipped += 1
+            return
+        self.optim.step()
+        self._ema_count += 1
+        if self._ema is not None:
+            with torch.no_grad():
+                if self._ema_count == 1:
+                    torch._foreach_copy_(self._ema, [p.detach() for p in params])
+                else:
+                    torch._foreach_lerp_(self._ema, [p.detach() for p in params], 1.0 - self.ema_decay)
+
+    def guard_state(self):
+        """{'grad_norm', 'clip_scale'} of the last step, 'skipped' (steps refused for a non-finite gradient) and 'steps' (steps taken);
+        one host read on the fused path.  ``skipped`` rising is the signal to reload a checkpoint: the guard keeps parameters,
+        moments, step count and average clean, but a non-finite FORWARD has already written into the running statistics."""
+        if not self._guarded:
+            raise ValueError('FlowTrainer was built without max_grad_norm / skip_nonfinite / ema_decay: there is no guard state')
+        if self._fused:
+            return self.optim.guard_state()
+        norm = float('nan') if self._last_norm is None else float(self._last_norm)
+        scale = 1.0 if self.max_grad_norm is None else min(1.0, self.max_grad_norm / (norm + 1.0e-6))
+        return {'grad_norm': norm, 'clip_scale': scale, 'skipped': self._skipped, 'steps': self._ema_count}
+
+    def ema_weights(self):
+        """context manager: inside it the parameters hold the averaged weights (swapped in place: nf_swap_f32 on the fused path, so a
+        captured graph's pointers stay valid and no copy of the bucket is made); on exit -- also by an exception -- the iterate is
+        back, bit for bit.  Buffers (running statistics) are not averaged and stay the live ones.  No training inside the block."""
+        if self.ema_decay is None:
+            raise ValueError('FlowTrainer.ema_weights() needs FlowTrainer(..., ema_decay=d)')
+        return _EmaWeights(self)
+
+    def _swap_ema(self):
+        if self._fused:
+            self.optim.swap_ema_()
+        else:
+            with torch.no_grad():
+                params = [p.detach() for p in self.bucket.params]
+                tmp = [p.clone() for p in params]
+                torch._foreach_copy_(params, self._ema)
+                torch._foreach_copy_(self._ema, tmp)
 
     def _capture(self, y):
         self._static_y = y.clone() if y is not None else None
@@ -464,7 +632,7 @@ class FlowTrainer:
             z, loss = self._forward_backward(self._static_y)
             if whole:
                 self.bucket.all_reduce_mean_()          # (no-op at world size 1)
-                self.optim.step()
+                self._optim_only()
             return z.detach(), loss.detach()
         g_fb = None
         if not single and self.one_graph:
@@ -485,7 +653,7 @@ class FlowTrainer:
         g_opt = None
         if not whole:                                   # N > 1: graph A, the flat bucket's all-reduce (eager, RCCL), graph B = Adam
             g_opt = self._graph_factory()
-            g_opt.capture(self.optim.step)
+            g_opt.capture(self._optim_only)
         self._g_fb, self._g_opt = g_fb, g_opt
         self._g_whole = whole
         from . import _native as N_
@@ -496,6 +664,9 @@ class FlowTrainer:
         Raises _native.PersistentKernelTimeout as soon as the host sees that a persistent kernel of an EARLIER launch gave up on
         a grid exchange (sticky pinned error word, no synchronisation: at most one step late)."""
         from . import _native as N
+        if self._in_ema:
+            raise RuntimeError('FlowTrainer.train_on_batch inside `with trainer.ema_weights():` -- the parameters hold the averaged '
+                               'weights there; leave the block before training')
         if y is None and self.sampler is None:
             raise ValueError('train_on_batch() without a batch needs FlowTrainer(..., sampler=data.DeviceSampler(...) or data.DeviceDataset(...))')
         if y is not None and y.is_cuda and y.device.index != torch.cuda.current_device():
@@ -585,9 +756,32 @@ class FlowTrainer:
         return float(self.optim.param_groups[0]['lr'])
 
     def save_ckpt(self, step, filename):
-        """{'net', 'optim', 'step'} with ``optim`` in torch.optim's format over net.parameters(): main.py:94-100"""
+        """{'net', 'optim', 'step'} with ``optim`` in torch.optim's format over net.parameters(): main.py:94-100.  With ``ema_decay``
+        also 'ema' and 'skipped'; without it the file is exactly the reference's."""
         optim = self.optim.torch_state_dict() if self._fused else _to_reference_layout(self.optim.state_dict(), self.bucket)
-        torch.save({'net': self.net.state_dict(), 'optim': optim, 'step': step}, filename)
+        ckpt = {'net': self.net.state_dict(), 'optim': optim, 'step': step}
+        if self.ema_decay is not None:
+            # two keys the reference's load_ckpt (main.py:102-107) never reads: the averaged TRAINABLE parameters by name, shaped like
+            # net.state_dict()'s entries, and the count of refused steps
+            if self._in_ema:
+                raise RuntimeError('FlowTrainer.save_ckpt inside `with trainer.ema_weights():` would save the average as the model')
+            ckpt['ema'] = {k: v.clone() for k, v in zip(self._ema_names(), self._ema_views())}
+            ckpt['skipped'] = self.guard_state()['skipped']
+        torch.save(ckpt, filename)
+
+    def _ema_names(self):
+        ids = {id(p): k for k, p in self.net.named_parameters()}
+        return [ids[id(p)] for p in self.bucket.params]
+
+    def _ema_views(self):
+        """the average as one tensor per bucketed parameter (views of the fused optimizer's flat buffer)"""
+        if not self._fused:
+            return self._ema
+        out, o = [], 0
+        for p in self.bucket.params:
+            out.append(self.optim.ema[o:o + p.numel()].view_as(p))
+            o += p.numel()
+        return out
 
     def load_ckpt(self, filename, resume_schedule=False):
         """main.py:102-107; returns the saved step.  Everything is copied INTO the tensors the trainer already holds, so a step that
@@ -625,6 +819,23 @@ class FlowTrainer:
                 self._sched._last_lr = [lr]
             else:
                 g.pop('initial_lr', None)
+        if self.ema_decay is not None:
+            # into the tensors that exist (a captured step goes on).  A file without 'ema' seeds the average from the loaded
+            # parameters; either way the next update blends instead of copying (ema_count >= 1 before it)
+            with torch.no_grad():
+                views = self._ema_views()
+                if 'ema' in ckpt:
+                    for k, v in zip(self._ema_names(), views):
+                        v.copy_(ckpt['ema'][k])
+                else:
+                    for p, v in zip(self.bucket.params, views):
+                        v.copy_(p.detach())
+                skipped = int(ckpt.get('skipped', 0))
+                if self._fused:
+                    self.optim.guard_ctl[3].fill_(skipped)
+                    self.optim.guard_ctl[4].clamp_(min=1)
+                else:
+                    self._skipped, self._ema_count = skipped, max(self._ema_count, 1)
         return step
 
     # -- evaluation -----------------------------------------------------------------------------------------------------
@@ -635,7 +846,7 @@ class FlowTrainer:
         return standard_normal_logprob(z) + ld
 
     @torch.no_grad()
-    def evaluate(self, dataset, graph=False, keep_rows=False):
+    def evaluate(self, dataset, graph=False, keep_rows=False, ema=False):
         """held-out score of the model over a whole device-resident set: main.py:121-127 taken over every sample exactly once.
 
         ``dataset``  a data.DeviceDataset on the SWEEP schedule (``train_set.sweep_view()`` or ``DeviceDataset(..., sweep=True)``).
@@ -650,7 +861,12 @@ class FlowTrainer:
         ``keep_rows``  also returns 'rows': the float64 log p of this rank's valid samples in the order served (the data-set order for
         the identity order at world size 1).
         ``graph``  one step's launches are captured once and replayed for every step; a capture that raises warns and the sweep runs on
-        eager launches.  The model is left in eval(): the next train_on_batch() puts it back, captured or not."""
+        eager launches.  The model is left in eval(): the next train_on_batch() puts it back, captured or not.
+        ``ema``    score the averaged weights (``ema_decay``): the sweep runs inside ``ema_weights()``.  Running statistics (BatchNorm, flow
+        BatchNorm) are buffers, not parameters: they are not averaged and stay the live ones."""
+        if ema:
+            with self.ema_weights():
+                return self.evaluate(dataset, graph=graph, keep_rows=keep_rows)
         from . import _native as N
         from .models import Ffjord
         if not getattr(dataset, 'sweep', False):
@@ -718,7 +934,7 @@ class FlowTrainer:
         return res
 
     @torch.no_grad()
-    def report(self, y_data, n_samples=None, graph=False, generator=None, map_size=256, canvas=512, radius=2):
+    def report(self, y_data, n_samples=None, graph=False, generator=None, map_size=256, canvas=512, radius=2, ema=False):
         """what Model.report computes before matplotlib, tensorboard and the jpg writer take over (main.py:135-284), as numpy arrays
         from ONE host read: everything is queued on the current stream, copied to pinned memory, and synchronised once.  The panels
         (``*_rgb``, ``*_grid``) are uint8 HWC images rasterised on the device (csrc/report.hip) -- the data area alone, no axes, ticks,
@@ -733,7 +949,13 @@ class FlowTrainer:
         ``n_samples``  default: the reference's max(100, n) for vectors, max(64, n) for images.  ``generator``: of the latent draw.
         ``graph``      (2-D) the chain grid -> net(y) -> log p -> colours is captured once per map_size and replayed by later calls: its
                        input is a constant.  A capture that raises warns and the call continues eagerly, as in ``evaluate``.
+        ``ema``        draw and score with the averaged weights (``ema_decay``): the call runs inside ``ema_weights()``; running statistics
+                       are buffers and stay the live ones.
         The model is left in eval(), like log_py(): the next train_on_batch() puts it back, captured or not."""
+        if ema:
+            with self.ema_weights():
+                return self.report(y_data, n_samples=n_samples, graph=graph, generator=generator, map_size=map_size, canvas=canvas,
+                                   radius=radius)
         from . import report as _report
         return _report.report(self, y_data, n_samples=n_samples, graph=graph, generator=generator, map_size=map_size, canvas=canvas,
                               radius=radius)
