@@ -1296,6 +1296,39 @@ int nf_rmsprop_step(float* param, const float* grad, float* square_avg, int* ste
  * pos is the schedule's own counter (restarted by a checkpoint load), not Adam's bias-correction step.                  */
 int nf_lr_step_decay(float* lr, const double* base_lr, int* pos, int decay_steps, double decay_ratio, nf_stream_t stream);
 
+/* ---- linear warmup times a decay on the device (torch.optim.lr_scheduler.SequentialLR([LinearLR(start_factor, 1, W),
+ * CosineAnnealingLR | StepLR], milestones=[W]) stepped after every optim.step(): main.py:89-90 with the schedules Glow and Flow++ are
+ * published with; main.py:68-70 knows StepLR alone).  One thread, enqueued where nf_lr_step_decay is; lr, base_lr and pos are device
+ * memory, so a captured hipGraph follows the schedule on replay.  With p = pos[0] and t = max(p - warmup_steps, 0):
+ *   warm  = 1 for p >= warmup_steps, else warmup_start + (1 - warmup_start) * p / warmup_steps
+ *   decay = base_lr[0]                                                           NF_LR_CONST   (span, arg unused)
+ *         = base_lr[0] * arg ^ (t / span), integer power by repeated squaring    NF_LR_STEP    (span: decay_steps, arg: decay_ratio)
+ *         = arg + (base_lr[0] - arg) * (1 + cos(pi t / span)) / 2 for t < span,  NF_LR_COSINE  (span: cosine_steps, arg: lr_min)
+ *           arg for t >= span: the rate HOLDS at the floor (torch's CosineAnnealingLR swings back up past T_max)
+ * lr[0] = (float)(warm * decay), formed in double and rounded once; pos[0] = p + 1.
+ * NF_E_BADARG (before any launch): lr, base_lr or pos NULL; warmup_steps < 0; warmup_start outside (0, 1] with warmup_steps > 0; an
+ * unknown kind; span < 1 with NF_LR_STEP / NF_LR_COSINE; arg < 0 or NaN with NF_LR_COSINE.                                         */
+#define NF_LR_CONST 0
+#define NF_LR_STEP 1
+#define NF_LR_COSINE 2
+int nf_lr_schedule(float* lr, const double* base_lr, int* pos, int warmup_steps, double warmup_start, int kind, int span, double arg,
+                   nf_stream_t stream);
+
+/* ---- fused Adamax over flat buffers (torch.optim.Adamax as torch 2.10 writes it; Glow's optimizer -- the reference's switch,
+ * main.py:56-66, names Adam and RMSprop only) ------------------------------------------------------------------------------------
+ * step[0] += 1, then for every i < n:  g = grad[i]*grad_scale + wd*p ; m += (1 - b1)(g - m) ; u = max(b2 u, |g| + eps) ;
+ * p -= (lr[0] / (1 - b1^step)) * m / u.  u >= eps > 0 after the first step: a zero gradient on a zero exp_inf divides by eps.
+ * 28 B per element like nf_adam_step (16 read, 12 written); one launch, float4 where all four buffers are 16-byte aligned with the
+ * last n % 4 elements in the same launch, scalar otherwise.
+ * NF_E_BADARG: n < 0, any pointer NULL with n > 0.  n = 0: nothing is launched.                                                    */
+int nf_adamax_step(float* param, const float* grad, float* exp_avg, float* exp_inf, int* step, const float* lr, float beta1,
+                   float beta2, float eps, float weight_decay, float grad_scale, int64_t n, nf_stream_t stream);
+/* ---- fused AdamW over flat buffers (torch.optim.AdamW = Adam with decoupled_weight_decay) -------------------------------------
+ * nf_adam_step's signature.  step[0] += 1, then for every i < n:  p *= 1 - lr[0]*wd ; g = grad[i]*grad_scale (NO wd*p term) ;
+ * Adam's moments and update (nf_adam_step's arithmetic).  Same bytes, same launch shape and errors as nf_adamax_step.             */
+int nf_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int* step, const float* lr, float beta1,
+                  float beta2, float eps, float weight_decay, float grad_scale, int64_t n, nf_stream_t stream);
+
 /* ---- the guarded step: clipping, non-finite skip and averaged weights inside the train step (main.py:78-92) ---------------------
  * The control block lives in device memory (zero it once); a captured hipGraph replays every decision without a host read.          */
 #define NF_GUARD_MAX_PARTIALS 1024        /* doubles in the partials slab nf_grad_guard is handed                                      */
@@ -1327,6 +1360,17 @@ int nf_adam_step_guarded(float* param, const float* grad, float* exp_avg, float*
                          int64_t n, nf_stream_t stream);
 int nf_rmsprop_step_guarded(float* param, const float* grad, float* square_avg, const float* lr, float alpha, float eps,
                             float weight_decay, const nf_guard_ctl* ctl, float* ema, float ema_decay, int64_t n, nf_stream_t stream);
+/* torch.optim.Adamax.step / torch.optim.AdamW.step (main.py:56-70, :89-90 with these two optimizers) after nf_grad_guard:
+ * nf_adamax_step's / nf_adamw_step's arithmetic with grad_scale = ctl->clip_scale -- on the gradient only, AdamW's decay factor
+ * 1 - lr wd is not scaled --, NO tick of step, and nothing read or written when ctl->skip is set: a skipped AdamW step does not
+ * decay the parameters either.  ema as in nf_adam_step_guarded, formed from the new parameter in the same pass.  One launch.
+ * NF_E_BADARG: n < 0, ctl NULL, any other pointer but ema NULL with n > 0.  n = 0: nothing is launched.                              */
+int nf_adamax_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_inf, const int* step, const float* lr,
+                           float beta1, float beta2, float eps, float weight_decay, const nf_guard_ctl* ctl, float* ema,
+                           float ema_decay, int64_t n, nf_stream_t stream);
+int nf_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const int* step, const float* lr,
+                          float beta1, float beta2, float eps, float weight_decay, const nf_guard_ctl* ctl, float* ema,
+                          float ema_decay, int64_t n, nf_stream_t stream);
 /* a[0 .. n) <-> b[0 .. n) in place, one launch: the averaged weights into the parameters for evaluation (main.py:121-124 on the
  * average) and back, without a temporary and without moving a pointer a captured graph holds.
  * NF_E_BADARG: n < 0, a or b NULL with n > 0, overlapping ranges (a == b is a no-op).                                                */

@@ -9,12 +9,15 @@
 //                            tick -- the optimizer's step and ema_count on a step that is taken, `skipped` on one that is not.
 //   nf_adam_step_guarded     k_adam_step's / nf_rmsprop_one's arithmetic (csrc/optim.hip) with grad_scale = ctl->clip_scale, nothing
 //   nf_rmsprop_step_guarded  touched when ctl->skip is set, and the average updated in the same pass from the new parameter.
+//   nf_adamax_step_guarded   the same for Adamax and AdamW (the element arithmetic of nf_optim_recipes.h, shared with csrc/optim.hip);
+//   nf_adamw_step_guarded    a skipped AdamW step does not apply the decoupled decay either.
 //   nf_swap_f32              in-place exchange of two flat buffers (the averaged weights into the parameters and back).
 // The result of the reduction depends on n and on the gradient's 16-byte alignment alone: the grid, the elements a thread takes and
 // the order of every addition are fixed by them, so two runs give the same bits whatever NF_DETERMINISTIC says.
 #include <math.h>
 
 #include "nf_common.h"
+#include "nf_optim_recipes.h"
 
 static inline unsigned nf_guard_grid(int64_t work_items) {
     int64_t g = (work_items + NF_BLOCK - 1) / NF_BLOCK;
@@ -277,6 +280,101 @@ extern "C" int nf_rmsprop_step_guarded(float* param, const float* grad, float* s
 #undef NF_LAUNCH_RMS_G
     NF_CHECK_LAUNCH();
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// the guarded Adamax and AdamW steps: the element arithmetic of nf_optim_recipes.h (what k_recipe_step of csrc/optim.hip runs) in
+// the template shape of the two kernels above.  A skipped step touches nothing -- AdamW's decoupled decay included: it is part of
+// the element's update, behind the same early return.
+// ---------------------------------------------------------------------------------------------------------------
+template <bool VEC, bool EMA, class R>
+__global__ void __launch_bounds__(NF_BLOCK) k_recipe_step_guarded(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                  float* __restrict__ s, const int* __restrict__ step,
+                                                                  const float* __restrict__ lr, NfRecipeHyper h,
+                                                                  const nf_guard_ctl* __restrict__ ctl, float* __restrict__ ema,
+                                                                  float ema_decay, int64_t n) {
+    if (ctl->skip != 0) return;                                    // uniform over the grid: nothing is touched
+    const float grad_scale = ctl->clip_scale;
+    const bool first = ctl->ema_count == 1;
+    const typename R::Consts c = R::consts(step, lr, h);
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, gstride = (int64_t)gridDim.x * blockDim.x;
+    int64_t done = 0;
+    if (VEC) {
+        const int64_t n4 = n / 4;
+        float4* __restrict__ p4 = reinterpret_cast<float4*>(p);
+        float4* __restrict__ m4 = reinterpret_cast<float4*>(m);
+        float4* __restrict__ s4 = reinterpret_cast<float4*>(s);
+        float4* __restrict__ e4 = reinterpret_cast<float4*>(ema);
+        const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
+        for (int64_t i = tid; i < n4; i += gstride) {
+            float4 pi = p4[i], mi = m4[i], si = s4[i];
+            const float4 gi = g4[i];
+            R::one(pi.x, gi.x, mi.x, si.x, c, grad_scale);
+            R::one(pi.y, gi.y, mi.y, si.y, c, grad_scale);
+            R::one(pi.z, gi.z, mi.z, si.z, c, grad_scale);
+            R::one(pi.w, gi.w, mi.w, si.w, c, grad_scale);
+            m4[i] = mi;
+            s4[i] = si;
+            p4[i] = pi;
+            if (EMA) {
+                float4 ei = pi;
+                if (!first) {
+                    ei = e4[i];
+                    ei.x = nf_ema_one(ei.x, pi.x, ema_decay, false);
+                    ei.y = nf_ema_one(ei.y, pi.y, ema_decay, false);
+                    ei.z = nf_ema_one(ei.z, pi.z, ema_decay, false);
+                    ei.w = nf_ema_one(ei.w, pi.w, ema_decay, false);
+                }
+                e4[i] = ei;
+            }
+        }
+        done = 4 * n4;
+    }
+    for (int64_t i = done + tid; i < n; i += gstride) {
+        float pi = p[i], mi = m[i], si = s[i];
+        R::one(pi, g[i], mi, si, c, grad_scale);
+        m[i] = mi;
+        s[i] = si;
+        p[i] = pi;
+        if (EMA) ema[i] = first ? pi : nf_ema_one(ema[i], pi, ema_decay, false);
+    }
+}
+
+template <class R>
+static int nf_recipe_step_guarded(float* param, const float* grad, float* m, float* s, const int* step, const float* lr, float beta1,
+                                  float beta2, float eps, float weight_decay, const nf_guard_ctl* ctl, float* ema, float ema_decay,
+                                  int64_t n, nf_stream_t stream) {
+    if (n < 0 || ctl == nullptr) return NF_E_BADARG;
+    if (n == 0) return 0;
+    if (param == nullptr || grad == nullptr || m == nullptr || s == nullptr || step == nullptr || lr == nullptr) return NF_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec = n >= 4 && nf_all_aligned16(param, grad, m, s, ema);
+    const dim3 grid(nf_grid_for(vec ? n / 4 : n)), block(NF_BLOCK);
+    const NfRecipeHyper h = nf_recipe_hyper(beta1, beta2, eps, weight_decay);
+#define NF_LAUNCH_RECIPE_G(V, E) \
+    hipLaunchKernelGGL((k_recipe_step_guarded<V, E, R>), grid, block, 0, st, param, grad, m, s, step, lr, h, ctl, ema, ema_decay, n)
+    if (vec) {
+        if (ema != nullptr) NF_LAUNCH_RECIPE_G(true, true); else NF_LAUNCH_RECIPE_G(true, false);
+    } else {
+        if (ema != nullptr) NF_LAUNCH_RECIPE_G(false, true); else NF_LAUNCH_RECIPE_G(false, false);
+    }
+#undef NF_LAUNCH_RECIPE_G
+    NF_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nf_adamax_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_inf, const int* step, const float* lr,
+                                      float beta1, float beta2, float eps, float weight_decay, const nf_guard_ctl* ctl, float* ema,
+                                      float ema_decay, int64_t n, nf_stream_t stream) {
+    return nf_recipe_step_guarded<NfAdamax>(param, grad, exp_avg, exp_inf, step, lr, beta1, beta2, eps, weight_decay, ctl, ema, ema_decay,
+                                            n, stream);
+}
+
+extern "C" int nf_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const int* step, const float* lr,
+                                     float beta1, float beta2, float eps, float weight_decay, const nf_guard_ctl* ctl, float* ema,
+                                     float ema_decay, int64_t n, nf_stream_t stream) {
+    return nf_recipe_step_guarded<NfAdamW>(param, grad, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay, ctl, ema,
+                                           ema_decay, n, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -44,9 +44,95 @@ def _check_ema_decay(d):
     return d
 
 
+class _LrRule:
+    """The learning-rate rule of the trainer, stated once for the fused path (whose launch, nf_lr_schedule, restates ``rate``) and the
+    torch.optim path.  With ``pos`` the optimizer steps completed under the schedule, W = lr_warmup_steps or 0 and
+    t = max(pos - W, 0), the step that follows trains at ``warm(pos) * decay(t)``:
+      warm   1 without a warmup, else lr_warmup_start + (1 - lr_warmup_start) min(pos, W) / W -- torch's LinearLR(start_factor, 1, W)
+      decay  base | base * decay_ratio ** (t // decay_steps) (StepLR, counted from the warmup's end) |
+             lr_min + (base - lr_min)(1 + cos(pi min(t, T) / T)) / 2 with T = cosine_steps.  Past t = T the rate HOLDS at lr_min;
+             torch's CosineAnnealingLR swings back up there.
+    ``general``: a warmup or a cosine is asked for, what the StepLR launch of ``decay_steps`` alone cannot do."""
+
+    def __init__(self, lr, decay_steps=None, decay_ratio=0.5, lr_warmup_steps=None, lr_warmup_start=1.0 / 3.0, cosine_steps=None,
+                 lr_min=0.0):
+        self.decay_steps = None if decay_steps is None else int(decay_steps)
+        self.decay_ratio = float(decay_ratio)
+        self.warmup_steps = None if lr_warmup_steps is None else int(lr_warmup_steps)
+        self.warmup_start = float(lr_warmup_start)
+        self.cosine_steps = None if cosine_steps is None else int(cosine_steps)
+        self.lr_min = float(lr_min)
+        if self.decay_steps is not None and self.decay_steps < 1:
+            raise ValueError('decay_steps must be a positive number of optimizer steps, got %r' % (decay_steps, ))
+        if self.warmup_steps is not None and self.warmup_steps < 1:
+            raise ValueError('lr_warmup_steps must be a positive number of optimizer steps, got %r' % (lr_warmup_steps, ))
+        if self.cosine_steps is not None and self.cosine_steps < 1:
+            raise ValueError('cosine_steps must be a positive number of optimizer steps, got %r' % (cosine_steps, ))
+        if self.decay_steps is not None and self.cosine_steps is not None:
+            raise ValueError('decay_steps (StepLR) and cosine_steps are two decays of the same rate: give one of them')
+        if not 0.0 < self.warmup_start <= 1.0:
+            raise ValueError('lr_warmup_start must lie in (0, 1] (torch\'s LinearLR refuses a start factor of 0), got %r' % (lr_warmup_start, ))
+        if not 0.0 <= self.lr_min <= float(lr):
+            raise ValueError('lr_min must lie in [0, lr = %r], got %r' % (float(lr), lr_min))
+        self.general = self.warmup_steps is not None or self.cosine_steps is not None
+        self.active = self.general or self.decay_steps is not None
+
+    def rate(self, base, pos):
+        base, pos, W = float(base), int(pos), self.warmup_steps or 0
+        t = max(pos - W, 0)
+        if self.decay_steps is not None:
+            d = base * self.decay_ratio ** (t // self.decay_steps)
+        elif self.cosine_steps is not None:
+            T = self.cosine_steps
+            d = self.lr_min if t >= T else self.lr_min + (base - self.lr_min) * (1.0 + math.cos(math.pi * t / T)) / 2.0
+        else:
+            d = base
+        if pos >= W:
+            return d
+        return (self.warmup_start + (1.0 - self.warmup_start) * pos / W) * d
+
+    def native_args(self):
+        """(warmup_steps, warmup_start, kind, span, arg) of nf_lr_schedule"""
+        from . import _native as N
+        if self.decay_steps is not None:
+            tail = (N.header_constant('NF_LR_STEP'), self.decay_steps, self.decay_ratio)
+        elif self.cosine_steps is not None:
+            tail = (N.header_constant('NF_LR_COSINE'), self.cosine_steps, self.lr_min)
+        else:
+            tail = (N.header_constant('NF_LR_CONST'), 0, 0.0)
+        return (self.warmup_steps or 0, self.warmup_start) + tail
+
+
+class _HostSchedule:
+    """``_LrRule`` on the torch.optim path where torch's StepLR does not cover it (a warmup, a cosine that holds at its floor): the
+    surface FlowTrainer uses of a torch scheduler -- ``step()`` after every optimizer step or replay, ``last_epoch`` -- writing the
+    group's ``lr`` (in place where it is the device tensor a captured framework optimizer reads) and ``initial_lr``."""
+
+    def __init__(self, optim, rule, base, pos=0):
+        self.optim, self.rule, self.base, self.last_epoch = optim, rule, float(base), int(pos)
+        self._write()
+
+    def _write(self):
+        g = self.optim.param_groups[0]
+        lr = self.rule.rate(self.base, self.last_epoch)
+        g['initial_lr'] = self.base
+        if isinstance(g['lr'], torch.Tensor):
+            g['lr'].fill_(lr)
+        else:
+            g['lr'] = lr
+        self._last_lr = [lr]
+
+    def step(self):
+        self.last_epoch += 1
+        self._write()
+
+    def get_last_lr(self):
+        return self._last_lr
+
+
 class _FlatOptimizer:
-    """What FlatAdam and FlatRMSprop share: ONE fused HIP launch over the flat parameter / gradient buffers of a GradBucket, with
-    ``lr`` and the step counter on the device, so that a captured hipGraph keeps working when the rate changes (``set_lr``).
+    """What the fused optimizers (FlatAdam, FlatRMSprop, FlatAdamax, FlatAdamW) share: ONE fused HIP launch over the flat
+    parameter / gradient buffers of a GradBucket, with ``lr`` and the step counter on the device, so that a captured hipGraph keeps working when the rate changes (``set_lr``).
 
     ``decay_steps`` (None: no schedule, no extra launch) puts torch's StepLR on the device (nf_lr_step_decay, one thread, enqueued
     in front of the optimizer launch and therefore part of a captured step): optimizer step t = 1, 2, ... since construction or the
@@ -54,16 +140,22 @@ class _FlatOptimizer:
     follows optim.step() (main.py:89-90).  ``sched_pos`` counts those steps; it is NOT ``step_count``, which a checkpoint carries on
     (Adam's bias correction) while the reference's schedule restarts at every load.  ``lr`` holds the rate in use.
 
+    ``lr_warmup_steps`` / ``lr_warmup_start`` / ``cosine_steps`` / ``lr_min`` (none given: the launches above and nothing else) put
+    the whole rule of ``_LrRule`` -- linear warmup times constant, StepLR or cosine decay, DESIGN.md 4.2 -- on the device instead:
+    nf_lr_schedule, one thread in the same place, reading the same ``base_lr`` and ``sched_pos``.
+
     ``max_grad_norm`` / ``skip_nonfinite`` / ``ema_decay`` (all off by default: the launches are then the plain ones) turn the
     optimizer launch into nf_grad_guard + the guarded step (csrc/optim_guard.hip): the gradient's 2-norm in float64,
     torch's clip scale and a skip flag in a device control block, the step reading both from there, the average ``ema`` updated in the
     same pass.  ``step_count`` does not advance on a skipped step; ``sched_pos`` does.  ``guard_state()`` reads the block.  Neither the
     average nor the skip count is torch optimizer state: ``torch_state_dict()`` does not carry them."""
 
-    KIND = None                     # 'Adam' / 'RMSprop': the torch.optim class whose state_dict format torch_state_dict() speaks
+    KIND = None                     # 'Adam' / 'RMSprop' / 'Adamax' / 'AdamW': the torch.optim class whose state_dict format torch_state_dict() speaks
     MOMENTS = ()                    # names of the per-parameter moment buffers, as torch.optim names them
 
-    def _init_common(self, bucket, lr, decay_steps, decay_ratio, max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
+    def _init_common(self, bucket, lr, decay_steps, decay_ratio, max_grad_norm=None, skip_nonfinite=False, ema_decay=None,
+                     **schedule_kw):
+        self._rule = _LrRule(lr, decay_steps, decay_ratio, **schedule_kw)
         if bucket.flat_params is None:
             raise ValueError('%s needs GradBucket(..., flatten_params=True)' % type(self).__name__)
         from . import _native as N
@@ -75,13 +167,12 @@ class _FlatOptimizer:
         self.step_count = torch.zeros(1, dtype=torch.int32, device=dev)
         self.lr = torch.full((1, ), float(lr), dtype=torch.float32, device=dev)
         self._lr_host = float(lr)   # the rate as the caller gave it (a double): what a checkpoint records while ``lr`` still rounds to it
-        self.decay_steps = None if decay_steps is None else int(decay_steps)
-        self.decay_ratio = float(decay_ratio)
-        if self.decay_steps is not None:
-            if self.decay_steps < 1:
-                raise ValueError('decay_steps must be a positive number of optimizer steps, got %r' % (decay_steps, ))
+        self.decay_steps, self.decay_ratio = self._rule.decay_steps, self._rule.decay_ratio
+        if self._rule.active:
             self.base_lr = torch.full((1, ), float(lr), dtype=torch.float64, device=dev)
             self.sched_pos = torch.zeros(1, dtype=torch.int32, device=dev)
+            if self._rule.general:
+                self.lr.fill_(self._rule.rate(lr, 0))   # (a warmup starts below the base rate)
         # the guarded step (csrc/optim_guard.hip).  With all three off none of the tensors below exists and _launch() issues the
         # plain nf_adam_step / nf_rmsprop_step; with any of them on it is nf_grad_guard followed by the guarded step
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
@@ -125,13 +216,14 @@ class _FlatOptimizer:
         """the rate of a trainer without a schedule, the BASE rate of one with a schedule"""
         self.lr.fill_(float(lr))
         self._lr_host = float(lr)
-        if self.decay_steps is not None:
+        if self._rule.active:
             self.base_lr.fill_(float(lr))
             self.lr.fill_(self.scheduled_lr(float(lr), int(self.sched_pos.item())))
 
     def scheduled_lr(self, base, pos):
-        """host restatement of nf_lr_step_decay: the rate of the step that follows ``pos`` completed ones"""
-        return float(base) * self.decay_ratio ** (int(pos) // self.decay_steps)
+        """host restatement of nf_lr_step_decay / nf_lr_schedule (``_LrRule.rate``): the rate of the step that follows ``pos``
+        completed ones"""
+        return self._rule.rate(base, pos)
 
     def set_schedule(self, base_lr, pos):
         """restart (pos = 0) or reposition the schedule; the state a captured graph reads is rewritten in place"""
@@ -151,7 +243,10 @@ class _FlatOptimizer:
     def step(self):
         N = self._N
         self._check_homed()
-        if self.decay_steps is not None:
+        if self._rule.general:
+            N.call('nf_lr_schedule', N.ptr(self.lr), N.ptr(self.base_lr, (torch.float64, )), N.ptr(self.sched_pos),
+                   *self._rule.native_args(), N.stream())
+        elif self.decay_steps is not None:
             N.call('nf_lr_step_decay', N.ptr(self.lr), N.ptr(self.base_lr, (torch.float64, )), N.ptr(self.sched_pos),
                    self.decay_steps, self.decay_ratio, N.stream())
         self._launch()
@@ -197,10 +292,10 @@ class _FlatOptimizer:
         lr = float(self.lr.item())
         if float(torch.tensor(self._lr_host, dtype=torch.float32)) == lr:
             lr = self._lr_host
-        if self.decay_steps is not None:                            # torch's group holds the rate of the NEXT step after scheduler.step()
+        if self._rule.active:                                       # torch's group holds the rate of the NEXT step after scheduler.step()
             lr = self.scheduled_lr(self.base_lr.item(), self.sched_pos.item())
         group = self._torch_group(lr)
-        if self.decay_steps is not None:
+        if self._rule.active:
             group['initial_lr'] = float(self.base_lr.item())        # (the key a torch scheduler adds to the group)
         group['params'] = list(range(b.n_all))
         return {'state': state, 'param_groups': [group]}
@@ -208,7 +303,9 @@ class _FlatOptimizer:
     def load_torch_state_dict(self, sd):
         """the reverse: moments and step into the flat buffers (in place, a captured graph goes on reading them), ``lr`` from the
         group.  The other hyper-parameters are launch arguments, frozen into a captured graph: they must equal this optimizer's.
-        A schedule, if any, restarts at position 0 from the loaded rate, as the reference's does after load_ckpt."""
+        A schedule, if any, restarts at position 0 from the loaded rate, as the reference's does after load_ckpt -- a poor fit for a
+        warmup, which then runs again from ``lr_warmup_start`` times the saved rate: ``FlowTrainer.load_ckpt(resume_schedule=True)``
+        (or ``set_schedule(base, pos)`` after this call) continues it instead."""
         groups = sd['param_groups']
         if len(groups) != 1:
             raise ValueError('%s holds one parameter group, the state dict has %d' % (type(self).__name__, len(groups)))
@@ -222,6 +319,9 @@ class _FlatOptimizer:
             if theirs != mine:
                 raise ValueError('%s was built with %s = %r, the state dict was written with %r; build the optimizer with the '
                                  'checkpoint\'s hyper-parameters' % (type(self).__name__, k, mine, theirs))
+        if bool(group.get('decoupled_weight_decay', False)) != (self.KIND == 'AdamW'):
+            raise ValueError('%s was built with decoupled_weight_decay = %r, the state dict was written with %r'
+                             % (type(self).__name__, self.KIND == 'AdamW', bool(group.get('decoupled_weight_decay', False))))
         for k in ('amsgrad', 'centered', 'maximize'):
             if group.get(k, False):
                 raise ValueError('%s does not implement %s=True' % (type(self).__name__, k))
@@ -248,7 +348,7 @@ class _FlatOptimizer:
             lr = float(group['lr'])
             self.lr.fill_(lr)
             self._lr_host = lr
-            if self.decay_steps is not None:
+            if self._rule.active:
                 self.set_schedule(lr, 0)
 
 
@@ -258,26 +358,53 @@ class FlatAdam(_FlatOptimizer):
     hipGraph keeps working when a scheduler changes the rate (``set_lr``, or the on-device StepLR of ``decay_steps``)."""
 
     KIND, MOMENTS = 'Adam', ('exp_avg', 'exp_avg_sq')
+    ENTRY = 'nf_adam_step'          # the plain launch; ENTRY + '_guarded' is the guarded one.  FlatAdamax and FlatAdamW differ in these
+                                    # three names (and their defaults) alone: the entry points share one argument list
 
     def __init__(self, bucket, lr=1.0e-4, betas=(0.9, 0.999), eps=1.0e-8, weight_decay=0.0, decay_steps=None, decay_ratio=0.5,
-                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, lr_warmup_steps=None, lr_warmup_start=1.0 / 3.0,
+                 cosine_steps=None, lr_min=0.0):
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
-        self._init_common(bucket, lr, decay_steps, decay_ratio, max_grad_norm, skip_nonfinite, ema_decay)
+        self._init_common(bucket, lr, decay_steps, decay_ratio, max_grad_norm, skip_nonfinite, ema_decay,
+                          lr_warmup_steps=lr_warmup_steps, lr_warmup_start=lr_warmup_start, cosine_steps=cosine_steps, lr_min=lr_min)
 
     def _hyper(self):
         return {'betas': (float(self.betas[0]), float(self.betas[1])), 'eps': self.eps, 'weight_decay': self.weight_decay}
 
     def _launch(self):
         N, b = self._N, self.bucket
+        m, s = (getattr(self, k) for k in self.MOMENTS)
         if self.guarded:
             self._guard()
-            N.call('nf_adam_step_guarded', N.ptr(b.flat_params), N.ptr(b.flat), N.ptr(self.exp_avg), N.ptr(self.exp_avg_sq),
+            N.call(self.ENTRY + '_guarded', N.ptr(b.flat_params), N.ptr(b.flat), N.ptr(m), N.ptr(s),
                    N.ptr(self.step_count), N.ptr(self.lr), self.betas[0], self.betas[1], self.eps, self.weight_decay,
                    N.ptr(self.guard_ctl), N.ptr(self.ema), self.ema_decay or 0.0, b.numel, N.stream())
             return
-        N.call('nf_adam_step', N.ptr(b.flat_params), N.ptr(b.flat), N.ptr(self.exp_avg), N.ptr(self.exp_avg_sq),
+        N.call(self.ENTRY, N.ptr(b.flat_params), N.ptr(b.flat), N.ptr(m), N.ptr(s),
                N.ptr(self.step_count), N.ptr(self.lr), self.betas[0], self.betas[1], self.eps, self.weight_decay, 1.0,
                b.numel, N.stream())
+
+
+class FlatAdamax(FlatAdam):
+    """torch.optim.Adamax (Glow's optimizer) as one fused HIP launch, nf_adamax_step: the second buffer is ``exp_inf``, the running
+    infinity norm max(beta2 u, |g| + eps), and only the first moment is bias-corrected.  Same surface and checkpoint format code as
+    FlatAdam: ``torch_state_dict()`` is what torch.optim.Adamax writes and loads."""
+
+    KIND, MOMENTS, ENTRY = 'Adamax', ('exp_avg', 'exp_inf'), 'nf_adamax_step'
+
+    def __init__(self, bucket, lr=2.0e-3, **kw):
+        super().__init__(bucket, lr=lr, **kw)
+
+
+class FlatAdamW(FlatAdam):
+    """torch.optim.AdamW -- Adam with DECOUPLED weight decay: p *= 1 - lr * weight_decay ahead of the update, no L2 term in the
+    gradient (which the weight-normed conditioners' ``weight_g`` takes badly) -- as one fused HIP launch, nf_adamw_step.  The group of
+    ``torch_state_dict()`` carries ``decoupled_weight_decay``; a guarded step that is skipped does not decay either."""
+
+    KIND, ENTRY = 'AdamW', 'nf_adamw_step'
+
+    def __init__(self, bucket, lr=1.0e-3, weight_decay=1.0e-2, **kw):
+        super().__init__(bucket, lr=lr, weight_decay=weight_decay, **kw)
 
 
 class FlatRMSprop(_FlatOptimizer):
@@ -287,9 +414,11 @@ class FlatRMSprop(_FlatOptimizer):
     KIND, MOMENTS = 'RMSprop', ('square_avg', )
 
     def __init__(self, bucket, lr=1.0e-2, alpha=0.99, eps=1.0e-8, weight_decay=0.0, decay_steps=None, decay_ratio=0.5,
-                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, lr_warmup_steps=None, lr_warmup_start=1.0 / 3.0,
+                 cosine_steps=None, lr_min=0.0):
         self.alpha, self.eps, self.weight_decay = alpha, eps, weight_decay
-        self._init_common(bucket, lr, decay_steps, decay_ratio, max_grad_norm, skip_nonfinite, ema_decay)
+        self._init_common(bucket, lr, decay_steps, decay_ratio, max_grad_norm, skip_nonfinite, ema_decay,
+                          lr_warmup_steps=lr_warmup_steps, lr_warmup_start=lr_warmup_start, cosine_steps=cosine_steps, lr_min=lr_min)
 
     def _hyper(self):
         return {'alpha': self.alpha, 'eps': self.eps, 'weight_decay': self.weight_decay}
@@ -366,6 +495,13 @@ class FlowTrainer:
     and inside the captured step with the fused optimizers, torch.optim.lr_scheduler.StepLR on the torch.optim path (CPU, or
     ``fused_adam=False``).  ``save_ckpt`` / ``load_ckpt`` speak the reference's checkpoint format (main.py:94-107).
 
+    Two parts of the published Glow / Flow++ recipes the reference's switch (main.py:56-70) does not offer, both opt-in:
+    ``optimizer='adamax' | 'adamw'`` -- FlatAdamax / FlatAdamW, one fused launch each, torch.optim.Adamax / AdamW on the torch.optim
+    path; and ``lr_warmup_steps`` / ``lr_warmup_start`` / ``cosine_steps`` / ``lr_min`` -- a linear warmup of the rate (these are NOT
+    ``warmup``, the eager steps before capture) times a constant, the StepLR of ``decay_steps`` counted from the warmup's end, or a
+    cosine decay to ``lr_min`` that holds there (``_LrRule``).  On the fused path the rule is one one-thread launch
+    inside the captured step (nf_lr_schedule); on the torch.optim path it is host code stepped after every step or replay.
+
     Three options the reference's loop (main.py:78-92) does not have, all off by default -- the step is then what it always was:
     ``max_grad_norm`` clips the global 2-norm of the (all-reduced) gradient as torch.nn.utils.clip_grad_norm_ does;
     ``skip_nonfinite`` leaves parameters, moments, step count and average untouched when that norm is not finite (the schedule
@@ -385,9 +521,12 @@ class FlowTrainer:
 
     def __init__(self, net, lr=1.0e-4, betas=(0.9, 0.999), weight_decay=0.0, graph=False, warmup=3, process_group=None,
                  fused_adam=True, sampler=None, sync_stats=False, graph_factory=None, one_graph=None, optimizer='adam',
-                 decay_steps=None, decay_ratio=0.5, max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
-        if optimizer not in ('adam', 'rmsprop'):
+                 decay_steps=None, decay_ratio=0.5, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, lr_warmup_steps=None,
+                 lr_warmup_start=1.0 / 3.0, cosine_steps=None, lr_min=0.0):
+        if optimizer not in ('adam', 'rmsprop', 'adamax', 'adamw'):
             raise Exception('optimizer "%s" is currently not supported' % (optimizer, ))       # (the reference's words, main.py:66)
+        sched_kw = dict(lr_warmup_steps=lr_warmup_steps, lr_warmup_start=lr_warmup_start, cosine_steps=cosine_steps, lr_min=lr_min)
+        self._rule = _LrRule(lr, decay_steps, decay_ratio, **sched_kw)
         self.net = net
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
@@ -433,14 +572,16 @@ class FlowTrainer:
         self.decay_steps = None if decay_steps is None else int(decay_steps)
         self.decay_ratio = float(decay_ratio)
         self._base_lr = float(lr)
-        self._sched = None          # the torch.optim path's StepLR (host side, stepped after every optimizer step or replay)
+        self._sched = None          # the torch.optim path's schedule (host side, stepped after every optimizer step or replay): torch's
+                                    # StepLR for decay_steps alone, _HostSchedule for a rule with a warmup or a cosine
         if fused_adam:
-            if optimizer == 'adam':
-                self.optim = FlatAdam(self.bucket, lr=lr, betas=betas, weight_decay=weight_decay, decay_steps=decay_steps,
-                                      decay_ratio=decay_ratio, **guard_kw)
-            else:
+            if optimizer == 'rmsprop':
                 self.optim = FlatRMSprop(self.bucket, lr=lr, weight_decay=weight_decay, decay_steps=decay_steps,
-                                         decay_ratio=decay_ratio, **guard_kw)
+                                         decay_ratio=decay_ratio, **guard_kw, **sched_kw)
+            else:
+                flat_cls = {'adam': FlatAdam, 'adamax': FlatAdamax, 'adamw': FlatAdamW}[optimizer]
+                self.optim = flat_cls(self.bucket, lr=lr, betas=betas, weight_decay=weight_decay, decay_steps=decay_steps,
+                                      decay_ratio=decay_ratio, **guard_kw, **sched_kw)
         else:
             capturable = self.graph and on_gpu
             if capturable and self.skip_nonfinite:
@@ -449,16 +590,19 @@ class FlowTrainer:
                                  '(fused_adam=True) or without graph=True')
             if self.ema_decay is not None:
                 self._ema = [p.detach().clone() for p in self.bucket.params]
-            if capturable and decay_steps is not None:
+            if capturable and self._rule.active:
                 # a captured framework optimizer reads a python-float rate once, at capture: the scheduler needs a device tensor to fill
                 lr = torch.tensor(float(lr), dtype=torch.float32, device=next(net.parameters()).device)
-            if optimizer == 'adam':
-                self.optim = torch.optim.Adam(self.bucket.params, lr=lr, betas=betas, weight_decay=weight_decay,
-                                              capturable=capturable, foreach=True)
-            else:
+            if optimizer == 'rmsprop':
                 self.optim = torch.optim.RMSprop(self.bucket.params, lr=lr, weight_decay=weight_decay, capturable=capturable,
                                                  foreach=True)
-            if decay_steps is not None:
+            else:
+                torch_cls = {'adam': torch.optim.Adam, 'adamax': torch.optim.Adamax, 'adamw': torch.optim.AdamW}[optimizer]
+                self.optim = torch_cls(self.bucket.params, lr=lr, betas=betas, weight_decay=weight_decay,
+                                       capturable=capturable, foreach=True)
+            if self._rule.general:
+                self._sched = _HostSchedule(self.optim, self._rule, self._base_lr)
+            elif decay_steps is not None:
                 self._sched = torch.optim.lr_scheduler.StepLR(self.optim, step_size=self.decay_steps, gamma=self.decay_ratio)
         self.warmup = warmup
         self._eager_steps = 0
@@ -752,7 +896,7 @@ class FlowTrainer:
         """the rate the next optimizer step runs at (synchronises on the fused path)"""
         if self._fused:
             o = self.optim
-            return float(o.lr.item()) if o.decay_steps is None else o.scheduled_lr(o.base_lr.item(), o.sched_pos.item())
+            return o.scheduled_lr(o.base_lr.item(), o.sched_pos.item()) if o._rule.active else float(o.lr.item())
         return float(self.optim.param_groups[0]['lr'])
 
     def save_ckpt(self, step, filename):
@@ -787,7 +931,9 @@ class FlowTrainer:
         """main.py:102-107; returns the saved step.  Everything is copied INTO the tensors the trainer already holds, so a step that
         is captured in a hipGraph goes on replaying.  The reference saves no scheduler state: after a load its StepLR restarts at
         position 0 from the saved (already decayed) rate, and so does this one by default.  ``resume_schedule=True`` continues the
-        schedule instead: position ``ckpt['step']``, base rate the group's ``initial_lr`` (else the rate this trainer was built with)."""
+        schedule instead: position ``ckpt['step']``, base rate the group's ``initial_lr`` (else the rate this trainer was built with).
+        A restart is a poor fit for a rule with a warmup (``lr_warmup_steps``): the warmup runs again, from ``lr_warmup_start`` times
+        the saved rate -- which is itself mid-schedule.  Load such a run with ``resume_schedule=True``."""
         if not self._fused and isinstance(self._g_fb, _HipStepGraph):
             raise RuntimeError('FlowTrainer: torch.optim.load_state_dict re-binds the state tensors a captured hipGraph reads; load the '
                                'checkpoint before the step is captured, or train with the fused optimizers (fused_adam=True)')
@@ -800,19 +946,21 @@ class FlowTrainer:
         pos = int(step) if resume_schedule else 0
         if self._fused:
             self.optim.load_torch_state_dict(ckpt['optim'])
-            if self.decay_steps is not None:
+            if self._rule.active:
                 self.optim.set_schedule(base, pos)
         else:
             lr_slot = self.optim.param_groups[0]['lr']          # (a device tensor when the framework optimizer is captured)
             self.optim.load_state_dict(_from_reference_layout(ckpt['optim'], self.bucket))
             g = self.optim.param_groups[0]
-            if self.decay_steps is not None:
-                lr = base * self.decay_ratio ** (pos // self.decay_steps)
+            if self._rule.active:
+                lr = self._rule.rate(base, pos)
             if isinstance(lr_slot, torch.Tensor):
                 g['lr'] = lr_slot.fill_(lr)
             else:
                 g['lr'] = lr
-            if self.decay_steps is not None:
+            if self._rule.general:
+                self._sched = _HostSchedule(self.optim, self._rule, base, pos)
+            elif self.decay_steps is not None:
                 g['initial_lr'] = base
                 self._sched = torch.optim.lr_scheduler.StepLR(self.optim, step_size=self.decay_steps, gamma=self.decay_ratio)
                 self._sched.last_epoch = pos
