@@ -288,6 +288,31 @@ int nf_mixlogcdf_bwd(const float* g_out, const float* g_ld, const float* x, cons
 int nf_mixlogcdf_inv(const float* target, const float* log_pi, const float* mu, const float* s, float* x, float* ld,
                      float* scratch, int* stuck_flag, int K, int64_t B, int64_t n, nf_stream_t stream);
 
+/* ---- monotone rational-quadratic spline coupling  Durkan et al. 2019, "Neural Spline Flows" (no reference function: the
+ * equations of the paper are cited) ---------------------------------------------------------------------------------------
+ * params: conditioner output (B, (3K-1)*Ch, h, w); per transformed element 3K-1 raw values rw[0..K) | rh[0..K) | rd[0..K-1),
+ * parameter p of transformed channel m at channel p*Ch + m (the convention of nf_mixlog_coupling_*).  min = 1e-3.
+ *   widths  w_j = 2 bound (min + (1 - K min) softmax(rw)_j), heights h_j the same from rh                        (section 3.1)
+ *   knots   x_0 = y_0 = -bound, x_j = -bound + sum_{i<j} w_i, the last knot exactly +bound; bin sizes are knot differences
+ *   slopes  d_0 = d_K = 1, interior d_j = min + softplus(rd_{j-1} + log(expm1(1 - min))): zero parameters are the identity
+ *   inside  -bound < x < bound (strict): bin k = #{j in 1..K-1 : x >= x_j}, theta = (x - x_k) / W, s = H / W,
+ *             D = s + (d_k+1 + d_k - 2 s) theta (1 - theta)
+ *             y = y_k + H (s theta^2 + d_k theta (1 - theta)) / D                                                      (eq. 4)
+ *             log dy/dx = log(s^2 (d_k+1 theta^2 + 2 s theta (1 - theta) + d_k (1 - theta)^2)) - 2 log D               (eq. 5)
+ *   outside y = x bit for bit, log-det term 0 (linear tails, section 3.2)
+ * forward (inverse = 0): ld[b] += sum log dy/dx.  inverse != 0: the bin by y against the y knots, theta = 2 c / (-b - sqrt(max(b^2 - 4 a c, 0)))
+ * clamped to [0, 1] with a, b, c of eq. 6-8 (appendix A.1), x = x_k + theta W, ld[b] -= sum log dy/dx at that theta.
+ * y = merge(y0, z1) written in full (pass-through half copied).  The log-det sums use no float atomics: two runs give the same bits.
+ * K in {4, 8, 16} (NF_E_UNSUPPORTED otherwise); NF_E_BADARG: bound <= 0, NF_SPLIT_NONE, a shape the split does not take (odd C in mode
+ * 1D), a NULL pointer with B > 0 -- all before any launch.  B = 0: nothing is launched.                                             */
+int nf_rqs_coupling_fwd(const float* z, const float* params, float* y, float* ld, int K, float bound, int mode, int odd, int inverse,
+                        int64_t B, int C, int H, int W, nf_stream_t stream);
+/* autograd of the forward direction.  g_z is written in full (pass-through half = g_y; the gradient through the conditioner reaches z
+ * by the caller's autograd, as for the affine coupling); g_params has the layout of params and is WRITTEN in full, zeros where nothing
+ * depends on a parameter (elements outside the interval, bins the element is not in).  g_ld is read only.                          */
+int nf_rqs_coupling_bwd(const float* g_y, const float* g_ld, const float* z, const float* params, float* g_z, float* g_params, int K,
+                        float bound, int mode, int odd, int64_t B, int C, int H, int W, nf_stream_t stream);
+
 /* ---- Flow++ density step pair: the coupling above on two features (NF_SPLIT_1D, D = 2, K <= 8), followed by the NEXT flow
  * step's ActNorm (flows/flowpp.py:60-66 alternates ActNorm and coupling; flows/modules.py:246-249) in the same pass:
  *     h = (y - next_bias) / exp(next_log_scale),   ld += coupling log-det - sum_c next_log_scale[c]

@@ -956,6 +956,61 @@ def mixlog_coupling(z, params, a_log_scale, a_bias, ld, n_mixtures, mode, odd, i
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# rational-quadratic spline coupling (Durkan et al. 2019; csrc/rqspline.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+RQS_BINS = (4, 8, 16)           # the template instances of csrc/rqspline.hip
+
+
+class _RQSCoupling(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, params, ld, K, bound, mode, odd):
+        B, C, H, W = _bchw(z)
+        y = torch.empty_like(z)
+        N.call('nf_rqs_coupling_fwd', N.ptr(z), N.ptr(params), N.ptr(y), N.ptr(ld), K, bound, mode, int(odd), 0, B, C, H, W, N.stream())
+        ctx.save_for_backward(z, params)
+        ctx.meta = (K, bound, mode, int(odd))
+        ctx.mark_dirty(ld)
+        return y, ld
+
+    @staticmethod
+    def backward(ctx, g_y, g_ld):
+        z, params = ctx.saved_tensors
+        K, bound, mode, odd = ctx.meta
+        B, C, H, W = _bchw(z)
+        g_y, g_ld = _contig(g_y), _contig(g_ld)
+        g_z = torch.empty_like(z)
+        g_p = torch.empty_like(params)
+        N.call('nf_rqs_coupling_bwd', N.ptr(g_y), N.ptr(g_ld), N.ptr(z), N.ptr(params), N.ptr(g_z), N.ptr(g_p), K, bound, mode, odd,
+               B, C, H, W, N.stream())
+        return g_z, g_p, g_ld, None, None, None, None
+
+
+def rqs_coupling(z, params, ld, K, bound, mode, odd, inverse=False):
+    """the monotone rational-quadratic spline coupling of Neural Spline Flows given ``params`` = conditioner(z1), shape
+    (B, (3K - 1) Ch, h, w): split + spline + merge + log-det in one launch; linear tails outside (-bound, bound).  The inverse is
+    closed-form (one quadratic solve per element) and runs without building a graph, like ``mixlog_coupling``'s."""
+    z, params = _contig(z), _contig(params)
+    N.ptr(z)                                                                # raises the engine's "no CPU path" error
+    K, bound = int(K), float(bound)
+    if K not in RQS_BINS:
+        raise ValueError('the spline kernels are built for %s bins, got %d' % (' / '.join(str(k) for k in RQS_BINS), K))
+    if not bound > 0.0:
+        raise ValueError('the spline interval (-bound, bound) needs bound > 0, got %r' % bound)
+    half = _half_shape(z, mode)
+    want = (half[0], (3 * K - 1) * half[1]) + tuple(half[2:])
+    if tuple(params.shape) != want:
+        raise ValueError('conditioner output has shape %s, expected %s' % (tuple(params.shape), want))
+    ld = _owned_ld(ld)
+    if not inverse:
+        return _RQSCoupling.apply(z, params, ld, K, bound, mode, odd)
+    with torch.no_grad():
+        B, C, H, W = _bchw(z)
+        y = torch.empty_like(z)
+        N.call('nf_rqs_coupling_fwd', N.ptr(z), N.ptr(params), N.ptr(y), N.ptr(ld), K, bound, mode, int(odd), 1, B, C, H, W, N.stream())
+    return y, ld
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # standalone MixLogCDF (flows/modules.py:186-212)
 # ----------------------------------------------------------------------------------------------------------------------
 def _mixcdf_shapes(x, log_pi):

@@ -18,7 +18,8 @@ What the reference's OWN graph contains is reproduced, no more:
   * ``PlanarTransform.backward`` bisects the same way (flows/planar.py:53-61): its midpoint is a constant, ``b``, ``u`` and ``w`` receive
     gradient through ``affine = mid + b``, ``z - u tanh(affine)`` and the log-det term (planar.py:63-66).
 Not served (NotImplementedError, as before): the MAF inverse (the reference writes columns of ``z`` in place between conditioner calls,
-flows/maf.py:109-119: its own graph does not survive that) and the fixed-point inverse of the residual blocks.
+flows/maf.py:109-119: its own graph does not survive that), the fixed-point inverse of the residual blocks and the inverse of the spline
+coupling (RQSplineCoupling has no reference graph to reproduce).
 """
 import contextlib
 
@@ -154,5 +155,5 @@ def layer_inverse(layer, y, ld):
         return y - layer.u * th, ld - torch.sum(torch.log(torch.abs(det) + 1.0e-5), dim=1)
     if isinstance(layer, L.CNF):                                     # cnf.py:160-173: the same adjoint Function, times as stored
         return layer.backward(y, ld)
-    raise NotImplementedError('the inverse of %s has no autograd graph in this engine (see inverse_grad.py: the MAF and residual-block '
-                              'inverses); detach the input or differentiate the forward direction' % type(layer).__name__)
+    raise NotImplementedError('the inverse of %s has no autograd graph in this engine (see inverse_grad.py: the MAF, residual-block '
+                              'and RQSplineCoupling inverses); detach the input or differentiate the forward direction' % type(layer).__name__)

@@ -986,6 +986,39 @@ class MixLogAttnCoupling(AbstractCoupling):
                                   self.odd, inverse=True)
 
 
+class RQSplineCoupling(AbstractCoupling):
+    """monotone rational-quadratic spline coupling of Neural Spline Flows (Durkan et al. 2019; no reference counterpart): the transformed
+    half goes through a ``bins``-piece spline on (-tail_bound, tail_bound) with linear tails, its 3 bins - 1 parameters per element come
+    from the conditioner of the affine coupling at that width.  Split + spline + merge + log-det are ONE kernel per direction, and the
+    inverse is closed-form.  The layer has no parameters of its own."""
+
+    def __init__(self, dims, masking='checkerboard', odd=False, bins=8, tail_bound=3.0):
+        super().__init__(dims, masking, odd)
+        if bins not in NF.RQS_BINS:
+            raise ValueError('RQSplineCoupling: bins must be one of %s, got %r' % (NF.RQS_BINS, bins))
+        if not float(tail_bound) > 0.0:
+            raise ValueError('RQSplineCoupling: tail_bound must be positive, got %r' % tail_bound)
+        self.bins, self.tail_bound = int(bins), float(tail_bound)
+        if len(dims) == 1:
+            in_chs = dims[0] // 2 if not odd else (dims[0] + 1) // 2
+            self.out_chs = dims[0] - in_chs
+            self.net = MLP(in_chs, self.out_chs * (3 * self.bins - 1))
+        else:
+            in_out_chs = dims[0] * 2 if masking == 'checkerboard' else dims[0] // 2
+            self.out_chs = in_out_chs
+            self.net = ConvNet(in_out_chs, in_out_chs * (3 * self.bins - 1))
+
+    def _couple(self, z, log_df_dz, inverse):
+        params = self.net(self.conditioner_input(z))
+        return NF.rqs_coupling(z, params, log_df_dz, self.bins, self.tail_bound, self.mode, self.odd, inverse=inverse)
+
+    def forward(self, z, log_df_dz):
+        return self._couple(z, log_df_dz, False)
+
+    def backward(self, y, log_df_dz):
+        return self._couple(y, log_df_dz, True)
+
+
 # ---- MAF (flows/maf.py) -------------------------------------------------------------------------------------------------
 
 class MADE(nn.Module):

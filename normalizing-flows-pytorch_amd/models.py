@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from .layers import (CNF, ActNorm, AffineCoupling, AutoregressiveTransfrom, BatchNorm, Compose, InvertibleConv1x1, Logit,
-                     MixLogAttnCoupling, PlanarTransform, Squeeze2d, Unsqueeze2d)
+                     MixLogAttnCoupling, PlanarTransform, RQSplineCoupling, Squeeze2d, Unsqueeze2d)
 
 
 class _FlowModel(nn.Module):
@@ -175,6 +175,16 @@ class Flowpp(_FlowModel):
             layers.append(InvertibleConv1x1(dims[0]))
         layers.append(MixLogAttnCoupling(dims, masking=masking, odd=odd, n_mixtures=cfg.mixtures))
         return layers
+
+
+class SplineFlow(_FlowModel):
+    """Neural spline flow (Durkan et al. 2019; no reference counterpart): Glow's step with the affine coupling replaced by the
+    rational-quadratic spline coupling.  cfg.bins (default 8) and cfg.tail_bound (default 3.0) are optional.  Vector data is the supported
+    workload; the image layout is the shared multi-scale recipe."""
+
+    def _step(self, dims, masking, odd, cfg):
+        return [ActNorm(dims), InvertibleConv1x1(dims[0]),
+                RQSplineCoupling(dims, masking=masking, odd=odd, bins=getattr(cfg, 'bins', 8), tail_bound=getattr(cfg, 'tail_bound', 3.0))]
 
 
 class MAF(_FlowModel):
