@@ -1304,14 +1304,18 @@ int nf_nll_loss_bwd(const float* z, const float* g_loss, float* g_z, float* g_ld
 
 /* ---- fused Adam over flat buffers (torch.optim.Adam semantics, main.py:56-64) --------------------------------------
  * step[0] += 1 (device int32), then for every i < n:  g = grad[i]*grad_scale + wd*p ; m,v moments ; p update with the
- * bias corrections of step[0] and the learning rate lr[0] (device float, so hipGraph replays see new values).     */
+ * bias corrections of step[0] and the learning rate lr[0] (device float, so hipGraph replays see new values).
+ * 28 B per element (16 read, 12 written); one launch behind the tick, float4 where all four buffers are 16-byte aligned with the
+ * last n % 4 elements in the same launch, scalar otherwise.
+ * NF_E_BADARG: n < 0, any pointer NULL with n > 0.  n = 0: nothing is launched.                                        */
 int nf_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int* step, const float* lr,
                  float beta1, float beta2, float eps, float weight_decay, float grad_scale, int64_t n,
                  nf_stream_t stream);
 
 /* ---- fused RMSprop over flat buffers (torch.optim.RMSprop with momentum 0, not centred: main.py:56-59) ----------------
  * step[0] += 1 (device int32), then for every i < n:  g = grad[i]*grad_scale + wd*p ; v = alpha v + (1-alpha) g^2 ;
- * p -= lr[0] * g / (sqrt(v) + eps).  One launch over the flat buffers (float4 where they are 16-byte aligned).       */
+ * p -= lr[0] * g / (sqrt(v) + eps).  20 B per element (12 read, 8 written); launch shape as nf_adam_step's.
+ * NF_E_BADARG: n < 0, any pointer NULL with n > 0.  n = 0: nothing is launched.                                        */
 int nf_rmsprop_step(float* param, const float* grad, float* square_avg, int* step, const float* lr, float alpha, float eps,
                     float weight_decay, float grad_scale, int64_t n, nf_stream_t stream);
 

@@ -1,12 +1,15 @@
-// Fused Adam over flat parameter / gradient / moment buffers: the whole optimizer step is ONE launch (+ a 1-thread
-// step-counter bump), instead of the thousands of per-parameter scalar kernels a capturable framework Adam issues for
-// the ~1100 small tensors of a 32-step flow.  Semantics = torch.optim.Adam (no amsgrad), which is what the reference
-// trains with (main.py:56-64, configs/default.yaml:13-20):
-//   g += wd * p ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ;
-//   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// The fused optimizer steps over flat parameter / gradient / state buffers: the whole step is ONE launch (+ a 1-thread step-counter
+// bump on the plain path), instead of the thousands of per-parameter scalar kernels a capturable framework optimizer issues for the
+// ~1100 small tensors of a 32-step flow.  Four recipes -- Adam and RMSprop, which the reference trains with (main.py:56-64,
+// configs/default.yaml:13-20), Adamax and AdamW (Glow's and the weight-normed conditioners') -- whose element arithmetic is
+// csrc/nf_optim_recipes.h, in ONE kernel body, k_optim_step<R, VEC, MODE>, behind ONE launcher and eight entry points:
+//   nf_X_step           plain: step[0] += 1 (k_adam_tick), then the stream with grad_scale as the caller gives it;
+//   nf_X_step_guarded   after nf_grad_guard (csrc/optim_guard.hip, which ticks): grad_scale = ctl->clip_scale, nothing touched when
+//                       ctl->skip is set -- AdamW's decoupled decay included, it is part of the element's update behind the same early
+//                       return --, and with ema != NULL the averaged weights updated in the same pass from the new parameter.
 // `step` and `lr` live in device memory so that a captured hipGraph replays with the right values.
-// Below it: the same for RMSprop (nf_rmsprop_step), Adamax and AdamW (nf_adamax_step, nf_adamw_step), and the schedules as one-thread
-// launches: StepLR (nf_lr_step_decay) and linear warmup times constant / step / cosine decay (nf_lr_schedule).
+// Below them the schedules as one-thread launches: StepLR (nf_lr_step_decay) and linear warmup times constant / step / cosine decay
+// (nf_lr_schedule); and nf_multi_copy.
 #include <math.h>
 
 #include "nf_common.h"
@@ -14,176 +17,152 @@
 
 __global__ void k_adam_tick(int* __restrict__ step) { step[0] += 1; }
 
-__global__ void __launch_bounds__(NF_BLOCK) k_adam_step(float* __restrict__ p, const float* __restrict__ g,
-                                                        float* __restrict__ m, float* __restrict__ v,
-                                                        const int* __restrict__ step, const float* __restrict__ lr,
-                                                        float b1, float b2, float eps, float wd, float grad_scale,
-                                                        int64_t n) {
-    const float t = (float)step[0];
-    const float bc1 = 1.f - powf(b1, t);
-    const float bc2_sqrt = sqrtf(1.f - powf(b2, t));
-    const float step_size = lr[0] / bc1;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float gi = g[i] * grad_scale;
-        const float pi = p[i];
-        if (wd != 0.f) gi = fmaf(wd, pi, gi);
-        const float mi = fmaf(b1, m[i], (1.f - b1) * gi);
-        const float vi = fmaf(b2, v[i], (1.f - b2) * gi * gi);
-        m[i] = mi;
-        v[i] = vi;
-        p[i] = pi - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+// ema = p_new on the first update that is taken (ActNorm initialises in the first forward), d ema + (1 - d) p_new afterwards
+__device__ __forceinline__ float nf_ema_one(float e, float p, float d) { return fmaf(d, e, (1.f - d) * p); }
+
+// A pure stream: per element 4 B of gradient read, 4 B of parameter and of each of the recipe's R::STATES buffers read and written (28 B
+// for the Adam family, 20 B for RMSprop, whose m is NULL and never formed into an address that is used), and 8 B more for the average
+// (4 B on the step that copies).  VEC: every buffer sits on 16 bytes, the body moves float4s and the last n % 4 elements take the scalar
+// form in the same launch; otherwise every element does.
+enum { NF_STEP_PLAIN, NF_STEP_GUARDED, NF_STEP_GUARDED_EMA };
+
+template <class R, bool VEC, int MODE>
+__global__ void __launch_bounds__(NF_BLOCK) k_optim_step(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ s, const int* __restrict__ step,
+                                                         const float* __restrict__ lr, NfOptimHyper h, float grad_scale,
+                                                         const nf_guard_ctl* __restrict__ ctl, float* __restrict__ ema, float ema_decay,
+                                                         int64_t n) {
+    constexpr bool TWO = R::STATES == 2, EMA = MODE == NF_STEP_GUARDED_EMA;
+    bool first = false;
+    if (MODE != NF_STEP_PLAIN) {                              // (the plain form does not read the control block)
+        if (ctl->skip != 0) return;                           // uniform over the grid: nothing is touched
+        grad_scale = ctl->clip_scale;
+        first = ctl->ema_count == 1;
     }
-}
-
-extern "C" int nf_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int* step,
-                            const float* lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
-                            int64_t n, nf_stream_t stream) {
-    if (n < 0) return NF_E_BADARG;
-    if (n == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(1), 0, st, step);
-    NF_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_adam_step, dim3(nf_grid_for(n)), dim3(NF_BLOCK), 0, st, param, grad, exp_avg, exp_avg_sq, step, lr,
-                       beta1, beta2, eps, weight_decay, grad_scale, n);
-    NF_CHECK_LAUNCH();
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Fused RMSprop over the same flat buffers: torch.optim.RMSprop with momentum = 0 and centered = False, the only form the
-// reference constructs (main.py:56-59):
-//   g += wd * p ; v = alpha v + (1 - alpha) g^2 ; p -= lr * g / (sqrt(v) + eps)
-// A pure stream, 12 B read and 8 B written per element.  Where the three flat buffers and the gradient are 16-byte aligned the
-// body moves float4s (VEC) and the last n % 4 elements take the scalar form in the same launch; otherwise every element does.
-// ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void nf_rmsprop_one(float& p, float g, float& v, float lr, float alpha, float eps, float wd,
-                                               float grad_scale) {
-    float gi = g * grad_scale;
-    if (wd != 0.f) gi = fmaf(wd, p, gi);
-    v = fmaf(alpha, v, (1.f - alpha) * gi * gi);
-    p = p - lr * (gi / (sqrtf(v) + eps));
-}
-
-template <bool VEC>
-__global__ void __launch_bounds__(NF_BLOCK) k_rmsprop_step(float* __restrict__ p, const float* __restrict__ g,
-                                                           float* __restrict__ v, const float* __restrict__ lr_ptr, float alpha,
-                                                           float eps, float wd, float grad_scale, int64_t n) {
-    const float lr = lr_ptr[0];
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, gstride = (int64_t)gridDim.x * blockDim.x;
-    int64_t done = 0;                                     // elements [0, done) are covered by the float4 body
-    if (VEC) {
-        const int64_t n4 = n / 4;
-        float4* __restrict__ p4 = reinterpret_cast<float4*>(p);
-        float4* __restrict__ v4 = reinterpret_cast<float4*>(v);
-        const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
-        for (int64_t i = tid; i < n4; i += gstride) {
-            float4 pi = p4[i], vi = v4[i];
-            const float4 gi = g4[i];
-            nf_rmsprop_one(pi.x, gi.x, vi.x, lr, alpha, eps, wd, grad_scale);
-            nf_rmsprop_one(pi.y, gi.y, vi.y, lr, alpha, eps, wd, grad_scale);
-            nf_rmsprop_one(pi.z, gi.z, vi.z, lr, alpha, eps, wd, grad_scale);
-            nf_rmsprop_one(pi.w, gi.w, vi.w, lr, alpha, eps, wd, grad_scale);
-            v4[i] = vi;
-            p4[i] = pi;
-        }
-        done = 4 * n4;
-    }
-    for (int64_t i = done + tid; i < n; i += gstride) {
-        float pi = p[i], vi = v[i];
-        nf_rmsprop_one(pi, g[i], vi, lr, alpha, eps, wd, grad_scale);
-        v[i] = vi;
-        p[i] = pi;
-    }
-}
-
-extern "C" int nf_rmsprop_step(float* param, const float* grad, float* square_avg, int* step, const float* lr, float alpha,
-                               float eps, float weight_decay, float grad_scale, int64_t n, nf_stream_t stream) {
-    if (n < 0) return NF_E_BADARG;
-    if (n == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(1), 0, st, step);
-    NF_CHECK_LAUNCH();
-    const bool vec = n >= 4 && (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)square_avg) & 15) == 0;
-    if (vec)
-        hipLaunchKernelGGL(k_rmsprop_step<true>, dim3(nf_grid_for(n / 4)), dim3(NF_BLOCK), 0, st, param, grad, square_avg, lr, alpha,
-                           eps, weight_decay, grad_scale, n);
-    else
-        hipLaunchKernelGGL(k_rmsprop_step<false>, dim3(nf_grid_for(n)), dim3(NF_BLOCK), 0, st, param, grad, square_avg, lr, alpha,
-                           eps, weight_decay, grad_scale, n);
-    NF_CHECK_LAUNCH();
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Fused Adamax and AdamW over the same flat buffers (torch.optim.Adamax, torch.optim.AdamW; the reference's optimizer switch,
-// main.py:56-66, names neither -- Adamax is what Glow trains with, decoupled decay what the weight-normed conditioners want).
-// The element's arithmetic is nf_optim_recipes.h; both are 28-byte-per-element streams like k_adam_step (16 B read, 12 B written)
-// in k_rmsprop_step's shape: float4 lanes with the scalar tail in the same launch where all four buffers sit on 16 bytes.
-// ---------------------------------------------------------------------------------------------------------------
-template <bool VEC, class R>
-__global__ void __launch_bounds__(NF_BLOCK) k_recipe_step(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                          float* __restrict__ s, const int* __restrict__ step,
-                                                          const float* __restrict__ lr, NfRecipeHyper h, float grad_scale, int64_t n) {
     const typename R::Consts c = R::consts(step, lr, h);
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, gstride = (int64_t)gridDim.x * blockDim.x;
-    int64_t done = 0;                                     // elements [0, done) are covered by the float4 body
+    int64_t done = 0;                                         // elements [0, done) are covered by the float4 body
     if (VEC) {
         const int64_t n4 = n / 4;
         float4* __restrict__ p4 = reinterpret_cast<float4*>(p);
         float4* __restrict__ m4 = reinterpret_cast<float4*>(m);
         float4* __restrict__ s4 = reinterpret_cast<float4*>(s);
+        float4* __restrict__ e4 = reinterpret_cast<float4*>(ema);
         const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
         for (int64_t i = tid; i < n4; i += gstride) {
-            float4 pi = p4[i], mi = m4[i], si = s4[i];
+            float4 pi = p4[i], si = s4[i], mi = {};
+            if constexpr (TWO) mi = m4[i];
             const float4 gi = g4[i];
             R::one(pi.x, gi.x, mi.x, si.x, c, grad_scale);
             R::one(pi.y, gi.y, mi.y, si.y, c, grad_scale);
             R::one(pi.z, gi.z, mi.z, si.z, c, grad_scale);
             R::one(pi.w, gi.w, mi.w, si.w, c, grad_scale);
-            m4[i] = mi;
+            if constexpr (TWO) m4[i] = mi;
             s4[i] = si;
             p4[i] = pi;
+            if (EMA) {
+                float4 ei = pi;
+                if (!first) {
+                    ei = e4[i];
+                    ei.x = nf_ema_one(ei.x, pi.x, ema_decay);
+                    ei.y = nf_ema_one(ei.y, pi.y, ema_decay);
+                    ei.z = nf_ema_one(ei.z, pi.z, ema_decay);
+                    ei.w = nf_ema_one(ei.w, pi.w, ema_decay);
+                }
+                e4[i] = ei;
+            }
         }
         done = 4 * n4;
     }
     for (int64_t i = done + tid; i < n; i += gstride) {
-        float pi = p[i], mi = m[i], si = s[i];
+        float pi = p[i], si = s[i], mi = 0.f;
+        if constexpr (TWO) mi = m[i];
         R::one(pi, g[i], mi, si, c, grad_scale);
-        m[i] = mi;
+        if constexpr (TWO) m[i] = mi;
         s[i] = si;
         p[i] = pi;
+        if (EMA) ema[i] = first ? pi : nf_ema_one(ema[i], pi, ema_decay);
     }
 }
 
+template <class R, int MODE>
+static auto nf_step_kernel(bool vec) { return vec ? k_optim_step<R, true, MODE> : k_optim_step<R, false, MODE>; }
+
+// The launcher of all eight entry points.  m is the first moment (NULL for a one-state recipe), s the second buffer; guarded: ctl is
+// read and ema may be given, step has been ticked by nf_grad_guard; plain: ctl and ema are NULL and step is ticked here.
 template <class R>
-static int nf_recipe_step(float* param, const float* grad, float* m, float* s, int* step, const float* lr, float beta1, float beta2,
-                          float eps, float weight_decay, float grad_scale, int64_t n, nf_stream_t stream) {
-    if (n < 0) return NF_E_BADARG;
+static int nf_optim_step(bool guarded, float* param, const float* grad, float* m, float* s, const int* step, const float* lr,
+                         const NfOptimHyper& h, float grad_scale, const nf_guard_ctl* ctl, float* ema, float ema_decay, int64_t n,
+                         nf_stream_t stream) {
+    if (n < 0 || (guarded && ctl == nullptr)) return NF_E_BADARG;
     if (n == 0) return 0;
-    if (param == nullptr || grad == nullptr || m == nullptr || s == nullptr || step == nullptr || lr == nullptr) return NF_E_BADARG;
+    if (param == nullptr || grad == nullptr || s == nullptr || lr == nullptr) return NF_E_BADARG;
+    if ((R::STATES == 2 && m == nullptr) || ((R::USES_STEP || !guarded) && step == nullptr)) return NF_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(1), 0, st, step);
-    NF_CHECK_LAUNCH();
-    const bool vec = n >= 4 && (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)m | (uintptr_t)s) & 15) == 0;
-    const NfRecipeHyper h = nf_recipe_hyper(beta1, beta2, eps, weight_decay);
-    if (vec)
-        hipLaunchKernelGGL((k_recipe_step<true, R>), dim3(nf_grid_for(n / 4)), dim3(NF_BLOCK), 0, st, param, grad, m, s, step, lr, h,
-                           grad_scale, n);
-    else
-        hipLaunchKernelGGL((k_recipe_step<false, R>), dim3(nf_grid_for(n)), dim3(NF_BLOCK), 0, st, param, grad, m, s, step, lr, h,
-                           grad_scale, n);
+    if (!guarded) {
+        hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(1), 0, st, const_cast<int*>(step));      // (a plain entry point's step is int*)
+        NF_CHECK_LAUNCH();
+    }
+    const bool vec = n >= 4 && (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)m | (uintptr_t)s | (uintptr_t)ema) & 15) == 0;      // (NULL counts as aligned)
+    const auto kernel = !guarded ? nf_step_kernel<R, NF_STEP_PLAIN>(vec)
+                                 : ema != nullptr ? nf_step_kernel<R, NF_STEP_GUARDED_EMA>(vec) : nf_step_kernel<R, NF_STEP_GUARDED>(vec);
+    hipLaunchKernelGGL(kernel, dim3(nf_grid_for(vec ? n / 4 : n)), dim3(NF_BLOCK), 0, st, param, grad, m, s, step, lr, h,
+                       grad_scale, ctl, ema, ema_decay, n);
     NF_CHECK_LAUNCH();
     return 0;
 }
 
+extern "C" int nf_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int* step, const float* lr,
+                            float beta1, float beta2, float eps, float weight_decay, float grad_scale, int64_t n,
+                            nf_stream_t stream) {
+    return nf_optim_step<NfAdam>(false, param, grad, exp_avg, exp_avg_sq, step, lr, nf_adam_hyper(beta1, beta2, eps, weight_decay), grad_scale,
+                                 nullptr, nullptr, 0.f, n, stream);
+}
+
+extern "C" int nf_rmsprop_step(float* param, const float* grad, float* square_avg, int* step, const float* lr, float alpha,
+                               float eps, float weight_decay, float grad_scale, int64_t n, nf_stream_t stream) {
+    return nf_optim_step<NfRmsprop>(false, param, grad, nullptr, square_avg, step, lr, nf_rmsprop_hyper(alpha, eps, weight_decay), grad_scale,
+                                    nullptr, nullptr, 0.f, n, stream);
+}
+
 extern "C" int nf_adamax_step(float* param, const float* grad, float* exp_avg, float* exp_inf, int* step, const float* lr, float beta1,
                               float beta2, float eps, float weight_decay, float grad_scale, int64_t n, nf_stream_t stream) {
-    return nf_recipe_step<NfAdamax>(param, grad, exp_avg, exp_inf, step, lr, beta1, beta2, eps, weight_decay, grad_scale, n, stream);
+    return nf_optim_step<NfAdamax>(false, param, grad, exp_avg, exp_inf, step, lr, nf_adam_hyper(beta1, beta2, eps, weight_decay), grad_scale,
+                                   nullptr, nullptr, 0.f, n, stream);
 }
 
 extern "C" int nf_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int* step, const float* lr, float beta1,
                              float beta2, float eps, float weight_decay, float grad_scale, int64_t n, nf_stream_t stream) {
-    return nf_recipe_step<NfAdamW>(param, grad, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay, grad_scale, n, stream);
+    return nf_optim_step<NfAdamW>(false, param, grad, exp_avg, exp_avg_sq, step, lr, nf_adam_hyper(beta1, beta2, eps, weight_decay), grad_scale,
+                                  nullptr, nullptr, 0.f, n, stream);
+}
+
+extern "C" int nf_adam_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const int* step,
+                                    const float* lr, float beta1, float beta2, float eps, float weight_decay, const nf_guard_ctl* ctl,
+                                    float* ema, float ema_decay, int64_t n, nf_stream_t stream) {
+    return nf_optim_step<NfAdam>(true, param, grad, exp_avg, exp_avg_sq, step, lr,
+                                 nf_adam_hyper(beta1, beta2, eps, weight_decay), 1.f, ctl, ema, ema_decay, n, stream);
+}
+
+extern "C" int nf_rmsprop_step_guarded(float* param, const float* grad, float* square_avg, const float* lr, float alpha, float eps,
+                                       float weight_decay, const nf_guard_ctl* ctl, float* ema, float ema_decay, int64_t n,
+                                       nf_stream_t stream) {
+    return nf_optim_step<NfRmsprop>(true, param, grad, nullptr, square_avg, nullptr, lr, nf_rmsprop_hyper(alpha, eps, weight_decay), 1.f, ctl,
+                                    ema, ema_decay, n, stream);
+}
+
+extern "C" int nf_adamax_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_inf, const int* step, const float* lr,
+                                      float beta1, float beta2, float eps, float weight_decay, const nf_guard_ctl* ctl, float* ema,
+                                      float ema_decay, int64_t n, nf_stream_t stream) {
+    return nf_optim_step<NfAdamax>(true, param, grad, exp_avg, exp_inf, step, lr,
+                                   nf_adam_hyper(beta1, beta2, eps, weight_decay), 1.f, ctl, ema, ema_decay, n, stream);
+}
+
+extern "C" int nf_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const int* step, const float* lr,
+                                     float beta1, float beta2, float eps, float weight_decay, const nf_guard_ctl* ctl, float* ema,
+                                     float ema_decay, int64_t n, nf_stream_t stream) {
+    return nf_optim_step<NfAdamW>(true, param, grad, exp_avg, exp_avg_sq, step, lr,
+                                  nf_adam_hyper(beta1, beta2, eps, weight_decay), 1.f, ctl, ema, ema_decay, n, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

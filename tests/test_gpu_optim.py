@@ -13,10 +13,11 @@ import numpy as np
 import pytest
 import torch
 
+from tests._optim import SPECIAL, _close, _feed, _fresh, _pair
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 SHAPES = [(32, 32), (32, ), (1, ), (2, 32), (1, 2, 1, 1)]
-SPECIAL = [0.0, 1e-12, -1e-9, 1e-6, 3e4]
 OPTS = [('FlatAdam', 'Adam'), ('FlatRMSprop', 'RMSprop')]
 
 
@@ -26,35 +27,6 @@ def mods(pkg):
     return importlib.import_module(pkg.__name__ + '.train'), importlib.import_module(pkg.__name__ + '.dist')
 
 
-def _close(a, b, what):
-    a, b = a.detach().double().reshape(-1), b.detach().double().reshape(-1)
-    assert bool(torch.isfinite(a).all()), what
-    ratio = float(((a - b).abs() / (2e-6 + 2e-6 * b.abs())).max())
-    print('%s: %.3f of the bar' % (what, ratio))
-    assert ratio <= 1.0, '%s: %.3f of the bar 2e-6 + 2e-6 |x|' % (what, ratio)
-
-
-def _pair(mods, shapes, seed=0):
-    """parameters in a flat bucket and their clones for torch.optim"""
-    _, nfdist = mods
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    pa = [torch.nn.Parameter(torch.randn(s, device=DEV, generator=g)) for s in shapes]
-    pb = [torch.nn.Parameter(p.detach().clone()) for p in pa]
-    return pa, pb, nfdist.GradBucket(pa, flatten_params=True), g
-
-
-def _feed(bucket, pa, pb, g, special=False):
-    """the same fresh gradient into the bucket and into the clones' .grad"""
-    flat = torch.randn(bucket.numel, device=DEV, generator=g)
-    if special:
-        flat[:len(SPECIAL)] = torch.tensor(SPECIAL, device=DEV)
-    bucket.flat.copy_(flat)
-    o = 0
-    for b in pb:
-        b.grad = flat[o:o + b.numel()].view_as(b).clone()
-        o += b.numel()
-
-
 @pytest.mark.parametrize('wd', [0.0, 0.01])
 def test_flat_rmsprop_matches_torch_rmsprop(mods, wd):
     train, _ = mods
@@ -62,7 +34,7 @@ def test_flat_rmsprop_matches_torch_rmsprop(mods, wd):
     opt_a = train.FlatRMSprop(bucket, lr=1e-2, weight_decay=wd)
     opt_b = torch.optim.RMSprop(pb, lr=1e-2, weight_decay=wd)
     for it in range(7):
-        _feed(bucket, pa, pb, g, special=(it == 0))              # (step 0: the square average starts at zero under the tiny entries)
+        _feed(bucket, pb, _fresh(bucket, g, special=(it == 0)))     # (step 0: the square average starts at zero under the tiny entries)
         opt_a.step()
         opt_b.step()
         for k, (a, b) in enumerate(zip(pa, pb)):
@@ -113,7 +85,7 @@ def test_steplr_decays_inside_a_captured_graph(mods, flat_cls, torch_cls, ratio)
     opt_b = getattr(torch.optim, torch_cls)(pb, lr=1e-2, weight_decay=0.01)
     sched = torch.optim.lr_scheduler.StepLR(opt_b, step_size=2, gamma=ratio)
     start = bucket.flat_params.clone()
-    _feed(bucket, pa, pb, g)
+    _feed(bucket, pb, _fresh(bucket, g))
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -131,7 +103,7 @@ def test_steplr_decays_inside_a_captured_graph(mods, flat_cls, torch_cls, ratio)
         opt_a.step()
     assert int(opt_a.sched_pos) == 0                             # (a capture runs nothing)
     for it in range(7):
-        _feed(bucket, pa, pb, g, special=(it == 3))
+        _feed(bucket, pb, _fresh(bucket, g, special=(it == 3)))
         want_lr = np.float32(sched.get_last_lr()[0])             # the rate of THIS step: StepLR as it stood before it
         graph.replay()
         opt_b.step()
@@ -149,7 +121,7 @@ def test_no_schedule_means_no_schedule_state(mods):
     pa, pb, bucket, g = _pair(mods, SHAPES)
     opt = train.FlatAdam(bucket, lr=1e-3)
     assert opt.decay_steps is None and not hasattr(opt, 'sched_pos')
-    _feed(bucket, pa, pb, g)
+    _feed(bucket, pb, _fresh(bucket, g))
     opt.step()
     opt.set_lr(5e-4)
     assert float(opt.lr) == float(np.float32(5e-4))
@@ -162,14 +134,14 @@ def test_optimizer_state_travels_both_ways_on_the_device(mods, flat_cls, torch_c
     pa, pb, bucket, g = _pair(mods, SHAPES, seed=2)
     opt_a = getattr(train, flat_cls)(bucket, lr=1e-2, weight_decay=0.01)
     for _ in range(3):
-        _feed(bucket, pa, pb, g)
+        _feed(bucket, pb, _fresh(bucket, g))
         opt_a.step()
     with torch.no_grad():
         for a, b in zip(pa, pb):
             b.copy_(a)
     opt_b = getattr(torch.optim, torch_cls)(pb, lr=1e-2, weight_decay=0.01)
     opt_b.load_state_dict(opt_a.torch_state_dict())
-    _feed(bucket, pa, pb, g)
+    _feed(bucket, pb, _fresh(bucket, g))
     opt_a.step()
     opt_b.step()
     for k, (a, b) in enumerate(zip(pa, pb)):
@@ -179,7 +151,7 @@ def test_optimizer_state_travels_both_ways_on_the_device(mods, flat_cls, torch_c
     pa, pb, bucket, g = _pair(mods, SHAPES, seed=3)
     opt_b = getattr(torch.optim, torch_cls)(pb, lr=1e-2, weight_decay=0.01)
     for _ in range(3):
-        _feed(bucket, pa, pb, g)
+        _feed(bucket, pb, _fresh(bucket, g))
         opt_b.step()
     with torch.no_grad():
         for a, b in zip(pa, pb):
@@ -187,7 +159,7 @@ def test_optimizer_state_travels_both_ways_on_the_device(mods, flat_cls, torch_c
     opt_a = getattr(train, flat_cls)(bucket, lr=1e-2, weight_decay=0.01)
     opt_a.load_torch_state_dict(opt_b.state_dict())
     assert pa[0].data_ptr() == bucket.flat_params.data_ptr()
-    _feed(bucket, pa, pb, g)
+    _feed(bucket, pb, _fresh(bucket, g))
     opt_a.step()
     opt_b.step()
     for k, (a, b) in enumerate(zip(pa, pb)):

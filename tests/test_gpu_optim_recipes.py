@@ -17,10 +17,11 @@ import pytest
 import torch
 from torch.optim import lr_scheduler as S
 
+from tests._optim import SPECIAL, _close, _feed, _fresh, _pair
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 SHAPES = [(32, 32), (32, ), (1, ), (2, 32), (1, 2, 1, 1)]        # tests/test_gpu_optim.py
-SPECIAL = [0.0, 1e-12, -1e-9, 1e-6, 3e4]
 RECIPES = [('FlatAdamax', 'Adamax', 'nf_adamax_step'), ('FlatAdamW', 'AdamW', 'nf_adamw_step')]
 ALL = [('FlatAdam', 'Adam'), ('FlatRMSprop', 'RMSprop'), ('FlatAdamax', 'Adamax'), ('FlatAdamW', 'AdamW')]
 W, START, T, LR_MIN = 5, 0.25, 12, 1e-5
@@ -30,39 +31,6 @@ W, START, T, LR_MIN = 5, 0.25, 12, 1e-5
 def mods(pkg):
     pkg._native.load()
     return importlib.import_module(pkg.__name__ + '.train'), importlib.import_module(pkg.__name__ + '.dist')
-
-
-def _close(a, b, what):
-    a, b = a.detach().double().reshape(-1), b.detach().double().reshape(-1)
-    assert bool(torch.isfinite(a).all()), what
-    ratio = float(((a - b).abs() / (2e-6 + 2e-6 * b.abs())).max())
-    print('%s: %.3f of the bar' % (what, ratio))
-    assert ratio <= 1.0, '%s: %.3f of the bar 2e-6 + 2e-6 |x|' % (what, ratio)
-
-
-def _pair(mods, shapes, seed=0):
-    """parameters in a flat bucket and their clones for torch.optim"""
-    _, nfdist = mods
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    pa = [torch.nn.Parameter(torch.randn(s, device=DEV, generator=g)) for s in shapes]
-    pb = [torch.nn.Parameter(p.detach().clone()) for p in pa]
-    return pa, pb, nfdist.GradBucket(pa, flatten_params=True), g
-
-
-def _feed(bucket, pb, flat):
-    """the same gradient into the bucket and into the clones' .grad"""
-    bucket.flat.copy_(flat)
-    o = 0
-    for b in pb:
-        b.grad = flat[o:o + b.numel()].view_as(b).clone()
-        o += b.numel()
-
-
-def _fresh(bucket, g, special=False):
-    flat = torch.randn(bucket.numel, device=DEV, generator=g)
-    if special:
-        flat[:len(SPECIAL)] = torch.tensor(SPECIAL, device=DEV)
-    return flat
 
 
 def _all_close(opt_a, opt_b, pa, pb, what):

@@ -1,5 +1,6 @@
 """
-The guarded optimizer step on the MI355X (csrc/optim_guard.hip): the gradient norm and its control block, the skip of a non-finite step,
+The guarded optimizer step on the MI355X (csrc/optim_guard.hip and the guarded modes of csrc/optim.hip's step kernel): the gradient
+norm and its control block, the skip of a non-finite step,
 clipping against torch.nn.utils.clip_grad_norm_ + torch.optim, the averaged weights updated in the fused pass, nf_swap_f32, and all of
 it inside a captured FlowTrainer step (main.py:78-92 has none of the three; the yardsticks are torch's own).
 
@@ -15,10 +16,11 @@ import numpy as np
 import pytest
 import torch
 
+from tests._optim import SPECIAL, _close, _feed, _pair
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 SHAPES = [(32, 32), (32, ), (1, ), (2, 32), (1, 2, 1, 1)]        # tests/test_gpu_optim.py: 1 123 elements
-SPECIAL = [0.0, 1e-12, -1e-9, 1e-6, 3e4]
 OPTS = [('FlatAdam', 'Adam'), ('FlatRMSprop', 'RMSprop')]
 PARTIALS = 1024                                                  # NF_GUARD_MAX_PARTIALS
 ONE_PASS = PARTIALS * 256 * 4                                    # elements one pass of the float4 partials grid covers
@@ -30,14 +32,6 @@ REL = 2.0 ** -22
 def mods(pkg):
     pkg._native.load()
     return importlib.import_module(pkg.__name__ + '.train'), importlib.import_module(pkg.__name__ + '.dist')
-
-
-def _close(a, b, what):
-    a, b = a.detach().double().reshape(-1), b.detach().double().reshape(-1)
-    assert bool(torch.isfinite(a).all()), what
-    ratio = float(((a - b).abs() / (2e-6 + 2e-6 * b.abs())).max())
-    print('%s: %.3f of the bar' % (what, ratio))
-    assert ratio <= 1.0, '%s: %.3f of the bar 2e-6 + 2e-6 |x|' % (what, ratio)
 
 
 def _ctl(t):
@@ -108,24 +102,6 @@ def test_grad_norm_squares_that_overflow_float32(pkg, aligned):
 
 
 # ---- the non-finite step ------------------------------------------------------------------------------------------------------------------
-def _pair(mods, shapes, seed=0):
-    """parameters in a flat bucket and their clones for torch.optim (tests/test_gpu_optim.py)"""
-    _, nfdist = mods
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    pa = [torch.nn.Parameter(torch.randn(s, device=DEV, generator=g)) for s in shapes]
-    pb = [torch.nn.Parameter(p.detach().clone()) for p in pa]
-    return pa, pb, nfdist.GradBucket(pa, flatten_params=True), g
-
-
-def _feed(bucket, pb, flat):
-    """the same gradient into the bucket and into the clones' .grad"""
-    bucket.flat.copy_(flat)
-    o = 0
-    for b in pb:
-        b.grad = flat[o:o + b.numel()].view_as(b).clone()
-        o += b.numel()
-
-
 def _snapshot(opt):
     return [t.clone() for t in [opt.bucket.flat_params, opt.step_count, opt.ema] + [getattr(opt, k) for k in opt.MOMENTS]]
 

@@ -1,13 +1,14 @@
-"""What the fused Adamax and AdamW steps cost beside the fused Adam step, and what the warmup + cosine schedule launch costs the
-captured training step, on one GPU (csrc/optim.hip: nf_adamax_step, nf_adamw_step, nf_lr_schedule).
+"""What the fused optimizer steps cost, and what the warmup + cosine schedule launch costs the captured training step, on one GPU
+(csrc/optim.hip: the eight nf_X_step / nf_X_step_guarded entry points, nf_lr_schedule).
 
     python tools/optim_bench.py [--rounds 5] [--maf-layers 10] [--out profiles/r17_optim.txt]
 
 One process, so that every form shares the GPU and its state:
-    kernel  at the C4 model's bucket size (8 380 754 parameters): nf_adamax_step, nf_adamw_step and nf_adam_step -- the yardstick, the
-            same 28 B per element -- microseconds between two events over 50 calls, alternated, median (min .. max) of --rounds, and
-            the bytes each must move as a share of 8 TB/s.  A new kernel is within the yardstick when its median is no further above
-            nf_adam_step's than nf_adam_step's own min .. max spread in this run; if it is not, the line says by how much.
+    kernel  at the C4 model's bucket size (8 380 754 parameters): all eight step entry points of csrc/optim.hip, the guarded ones with
+            the average -- microseconds between two events over 50 calls, alternated, median (min .. max) of --rounds, and the bytes
+            each must move as a share of 8 TB/s.  nf_adam_step is the yardstick of the plain 28 B steps: one of them is within it when
+            its median is no further above nf_adam_step's than nf_adam_step's own min .. max spread in this run; if it is not, the
+            line says by how much.  The same rule compares two builds: an entry point's median against its own in the other build.
     step    the captured step of the C5 shape (MAF on `normals`, B = 16 384) without a schedule and with lr_warmup_steps +
             cosine_steps (one more one-thread node in the graph): --rounds alternated loops of 30 steps each, wall-clock microseconds
             per step, median (min .. max) over the loops
@@ -36,25 +37,36 @@ def _f(v):
     return '%10.2f (%.2f .. %.2f)' % tuple(v)
 
 
+ENTRIES = tuple('nf_%s_step%s' % (r, g) for g in ('', '_guarded') for r in ('adam', 'rmsprop', 'adamax', 'adamw'))
+
+
 def kernel_case(torch, pkg, n, rounds, dev):
     N = pkg._native
     g = torch.Generator(device=dev).manual_seed(0)
-    p, gr, m = (torch.randn(n, device=dev, generator=g) for _ in range(3))
+    p, gr, m, ema = (torch.randn(n, device=dev, generator=g) for _ in range(4))
     v = torch.rand(n, device=dev, generator=g)
     step, lr = torch.zeros(1, dtype=torch.int32, device=dev), torch.full((1, ), 1e-4, device=dev)
+    ctl = torch.zeros(8, dtype=torch.int32, device=dev)
+    partials = torch.zeros(N.header_constant('NF_GUARD_MAX_PARTIALS'), dtype=torch.float64, device=dev)
+    for _ in range(2):                                       # a control block that says "take it", past the step that copies the average
+        N.call('nf_grad_guard', gr.data_ptr(), n, 100.0, 1, partials.data_ptr(), ctl.data_ptr(), step.data_ptr(), N.stream())
 
     def form(entry):
-        return lambda: N.call(entry, p.data_ptr(), gr.data_ptr(), m.data_ptr(), v.data_ptr(), step.data_ptr(), lr.data_ptr(), 0.9, 0.999,
-                              1e-8, 0.01, 1.0, n, N.stream())
+        """(bytes the launch must move, the call): RMSprop has one state buffer, alpha for the betas and, guarded, no step argument"""
+        rms, guarded = 'rmsprop' in entry, entry.endswith('_guarded')
+        args = [p.data_ptr(), gr.data_ptr()] + ([] if rms else [m.data_ptr()]) + [v.data_ptr()]
+        args += ([] if rms and guarded else [step.data_ptr()]) + [lr.data_ptr()] + ([0.99] if rms else [0.9, 0.999]) + [1e-8, 0.01]
+        args += [ctl.data_ptr(), ema.data_ptr(), 0.999] if guarded else [1.0]
+        return 4 * n * ((5 if rms else 7) + (2 if guarded else 0)), lambda: N.call(entry, *args, n, N.stream())
 
-    forms = {name: form(name) for name in ('nf_adamax_step', 'nf_adamw_step', 'nf_adam_step')}
+    forms = {name: form(name) for name in ENTRIES}
     got = {k: [] for k in forms}
-    for fn in forms.values():
+    for _, fn in forms.values():
         for _ in range(5):
             fn()
     torch.cuda.synchronize()
     for _ in range(rounds):                                  # alternated
-        for name, fn in forms.items():
+        for name, (_, fn) in forms.items():
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
             for _ in range(50):
@@ -62,7 +74,7 @@ def kernel_case(torch, pkg, n, rounds, dev):
             b.record()
             torch.cuda.synchronize()
             got[name].append(a.elapsed_time(b) * 1e3 / 50)
-    return {'n': n, 'bytes': 28 * n, 'us': {k: _stats(got[k]) for k in forms}}
+    return {'n': n, 'bytes': {k: forms[k][0] for k in forms}, 'us': {k: _stats(got[k]) for k in forms}}
 
 
 def step_case(torch, pkg, train, nfdata, layers, rounds, dev):
@@ -118,19 +130,22 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    say('fused Adamax / AdamW beside fused Adam, and the schedule launch inside the captured step, %s' % torch.cuda.get_device_name(0))
+    say('the fused optimizer steps, and the schedule launch inside the captured step, %s' % torch.cuda.get_device_name(0))
     k = kernel_case(torch, pkg, a.numel, a.rounds, dev)
-    say('the launches alone at the C4 bucket size, n = %d (%.1f MB each): microseconds per call between two events over 50 calls, '
-        'median of %d alternated rounds (min .. max)' % (k['n'], k['bytes'] / 1e6, a.rounds))
+    say('the launches alone at the C4 bucket size, n = %d: microseconds per call between two events over 50 calls, median of %d '
+        'alternated rounds (min .. max)' % (k['n'], a.rounds))
     yard = k['us']['nf_adam_step']
     spread = yard[2] - yard[1]
     for name, us in k['us'].items():
-        note = 'the yardstick; its own spread %.2f us' % spread
-        if name != 'nf_adam_step':
+        note = ''
+        if name == 'nf_adam_step':
+            note = 'the yardstick of the 28 B plain steps; its own spread %.2f us' % spread
+        elif k['bytes'][name] == k['bytes']['nf_adam_step']:
             over = us[0] - yard[0]
             note = ('%+.2f us against the yardstick: within its spread' % over if over <= spread else
                     '%+.2f us against the yardstick: SLOWER than its spread of %.2f us allows, by %.2f us' % (over, spread, over - spread))
-        say('  %-16s %s   %5.1f %% of 8 TB/s   %s' % (name, _f(us), 100.0 * k['bytes'] / (us[0] * 1e-6) / HBM_PEAK, note))
+        say('  %-24s %s   %6.1f MB   %5.1f %% of 8 TB/s   %s' % (name, _f(us), k['bytes'][name] / 1e6,
+                                                                100.0 * k['bytes'][name] / (us[0] * 1e-6) / HBM_PEAK, note))
     s = step_case(torch, pkg, train, nfdata, a.maf_layers, a.rounds, dev)
     plain, sched = s['step_plain_us'], s['step_scheduled_us']
     say('MAF on normals, layers = %d, B = %d, bucket of %d parameters: microseconds per captured step, median of %d alternated '
