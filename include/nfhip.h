@@ -313,6 +313,35 @@ int nf_rqs_coupling_fwd(const float* z, const float* params, float* y, float* ld
 int nf_rqs_coupling_bwd(const float* g_y, const float* g_ld, const float* z, const float* params, float* g_z, float* g_params, int K,
                         float bound, int mode, int odd, int64_t B, int C, int H, int W, nf_stream_t stream);
 
+/* ---- autoregressive spline head: the masked output layer of a MADE-style conditioner and the spline above in ONE launch (the
+ * masked-autoregressive form of Neural Spline Flows; no reference function).  The (B, (3K-1)*D) parameter tensor and its gradient
+ * are never written to memory.  For a row with activated hidden vector a[0..H), feature d and parameter p in [0, 3K-1):
+ *     P[p] = bias[p*D + d] + sum_i a[i] * weight[p*D + d, i] * mask[d, i]
+ *     y_d  = rqs(z_d; P),   ld += log dy_d/dz_d          (the conventions of nf_rqs_coupling_* above: min 1e-3, the slope offset,
+ *                                                          the strict inside test, linear tails that pass bit for bit)
+ * a (B, H); weight ((3K-1)*D, H) and bias ((3K-1)*D): row p*D + d is the p*Ch + m order above with Ch = D; mask (D, H) of 0 / 1 floats,
+ * row d of it serves the 3K-1 weight rows of feature d; z, y (B, D); ld (B).
+ * nf_arspline_usable: 1 for 1 <= D <= 8, K in {4, 8, 16}, H == 32, else 0.
+ * nf_arspline_head_fwd, inverse = 0 (col must be -1): every feature is transformed, ld[b] += the sum of the D terms in feature order.
+ *   inverse != 0 (0 <= col < D): the parameters of feature `col` ALONE are formed, y[:, col] is the closed-form inverse of z[:, col]
+ *   and ld[b] -= that element's term; no other column of y is touched.  y may alias z.
+ * NF_E_UNSUPPORTED for a shape nf_arspline_usable rejects; NF_E_BADARG: bound <= 0, a col that does not fit the direction, B < 0 or
+ * B >= 2^31, a NULL pointer with B > 0 -- all before any launch.  B = 0: nothing is launched.                                        */
+int nf_arspline_usable(int D, int K, int H);
+int nf_arspline_head_fwd(const float* a, const float* weight, const float* bias, const float* mask, const float* z, float* y, float* ld,
+                         int K, float bound, int inverse, int col, int64_t B, int D, int H, nf_stream_t stream);
+/* autograd of the forward direction.  g_a (B, H) is written in full; g_z (B, D) is the DIRECT dependence on z_d alone (g_y outside the
+ * interval): the path through the conditioner reaches z through g_a and the caller's autograd, as for the couplings.  The weight and bias
+ * gradients leave as per-workgroup partial sums: g_w_slabs (n, (3K-1)*D, H) and g_b_slabs (n, (3K-1)*D), n = nf_arspline_head_slabs(B),
+ * every element WRITTEN (no zero fill), for nf_slab_sum to fold in slab order.  A weight-gradient element whose mask entry is 0 is
+ * exactly 0.  No float atomics: two runs give the same bits.                                                                         */
+#define NF_ARS_ROWS 128          /* rows (= threads) of a workgroup of the head kernels */
+#define NF_ARS_MAX_SLABS 1024
+int nf_arspline_head_slabs(int64_t B);
+int nf_arspline_head_bwd(const float* g_y, const float* g_ld, const float* a, const float* weight, const float* bias, const float* mask,
+                         const float* z, float* g_a, float* g_z, float* g_w_slabs, float* g_b_slabs, int K, float bound, int64_t B,
+                         int D, int H, nf_stream_t stream);
+
 /* ---- Flow++ density step pair: the coupling above on two features (NF_SPLIT_1D, D = 2, K <= 8), followed by the NEXT flow
  * step's ActNorm (flows/flowpp.py:60-66 alternates ActNorm and coupling; flows/modules.py:246-249) in the same pass:
  *     h = (y - next_bias) / exp(next_log_scale),   ld += coupling log-det - sum_c next_log_scale[c]

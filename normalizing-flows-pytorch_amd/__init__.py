@@ -9,14 +9,14 @@ The directory name is not a Python identifier; import it with
 """
 from . import _native, functional  # noqa: F401
 from ._build import build  # noqa: F401
-from .layers import (CNF, MADE, ActNorm, AbstractCoupling, AdditiveCoupling, AffineCoupling, AutoregressiveTransfrom, BatchNorm, Compose, Identity,
+from .layers import (CNF, MADE, ActNorm, AbstractCoupling, AdditiveCoupling, AffineCoupling, AutoregressiveSpline, AutoregressiveTransfrom, BatchNorm, Compose, Identity,
                      InvertibleConv1x1, Logit, MixLogAttnCoupling, MixLogCDF, PlanarTransform, RQSplineCoupling, Squeeze2d, Unsqueeze2d, Sigmoid, Tanh, Arctanh, Squeeze1d,
                      Unsqueeze1d, ConcatLinear, ODENet, odeint, odeint_adjoint)
 from .inverse_grad import differentiable_inverse  # noqa: F401
-from .models import MAF, Ffjord, Flowpp, Glow, PlanarFlow, RealNVP, SplineFlow
+from .models import MAF, Ffjord, Flowpp, Glow, PlanarFlow, RealNVP, SplineFlow, SplineMAF
 from .resflow import InvertibleResLinear, LipSwish, ResFlow, SpectralNorm
 
 __all__ = ['ActNorm', 'AbstractCoupling', 'AdditiveCoupling', 'AffineCoupling', 'BatchNorm', 'Compose', 'Identity', 'InvertibleConv1x1',
            'Logit', 'Squeeze2d', 'Unsqueeze2d', 'Glow', 'RealNVP', 'Flowpp', 'MAF', 'MADE', 'AutoregressiveTransfrom',
            'MixLogAttnCoupling', 'MixLogCDF', 'Sigmoid', 'Tanh', 'Arctanh', 'Squeeze1d', 'Unsqueeze1d', 'ResFlow', 'InvertibleResLinear', 'SpectralNorm', 'LipSwish', 'build', 'functional', 'differentiable_inverse', 'PlanarFlow',
-           'PlanarTransform', 'Ffjord', 'CNF', 'ODENet', 'ConcatLinear', 'RQSplineCoupling', 'SplineFlow']
+           'PlanarTransform', 'Ffjord', 'CNF', 'ODENet', 'ConcatLinear', 'RQSplineCoupling', 'SplineFlow', 'AutoregressiveSpline', 'SplineMAF']

@@ -1011,6 +1011,94 @@ def rqs_coupling(z, params, ld, K, bound, mode, odd, inverse=False):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# autoregressive spline head: masked output layer + spline in one launch (csrc/arspline.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+ARS_MAX_D = 8                   # features the head kernels serve
+ARS_HIDDEN = 32                 # hidden width they are built for
+
+
+class _ARSHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, weight, bias, mask, z, ld, K, bound):
+        B, D = z.shape
+        y = torch.empty_like(z)
+        N.call('nf_arspline_head_fwd', N.ptr(a), N.ptr(weight), N.ptr(bias), N.ptr(mask), N.ptr(z), N.ptr(y), N.ptr(ld), K, bound, 0, -1,
+               B, D, ARS_HIDDEN, N.stream())
+        ctx.save_for_backward(a, weight, bias, mask, z)
+        ctx.meta = (K, bound)
+        ctx.sinks = _sinks(weight, bias)
+        ctx.mark_dirty(ld)
+        return y, ld
+
+    @staticmethod
+    def backward(ctx, g_y, g_ld):
+        a, weight, bias, mask, z = ctx.saved_tensors
+        K, bound = ctx.meta
+        B, D = z.shape
+        g_y, g_ld = _contig(g_y), _contig(g_ld)
+        g_a, g_z = torch.empty_like(a), torch.empty_like(z)
+        rows = weight.shape[0]
+        n = int(N.load().nf_arspline_head_slabs(B))
+        if n == 0:                                                              # an empty batch: nothing depends on the parameters
+            return g_a, torch.zeros_like(weight), torch.zeros_like(bias), None, g_z, g_ld, None, None
+        # per-workgroup partial sums of the weight and bias gradients, every element written by the launch; one nf_slab_sum folds both
+        slabs = torch.empty(n * rows * (ARS_HIDDEN + 1), dtype=torch.float32, device=z.device)
+        gw_s, gb_s = slabs[:n * rows * ARS_HIDDEN], slabs[n * rows * ARS_HIDDEN:]
+        N.call('nf_arspline_head_bwd', N.ptr(g_y), N.ptr(g_ld), N.ptr(a), N.ptr(weight), N.ptr(bias), N.ptr(mask), N.ptr(z), N.ptr(g_a),
+               N.ptr(g_z), N.ptr(gw_s), N.ptr(gb_s), K, bound, B, D, ARS_HIDDEN, N.stream())
+        from .fused_conv import _slab_sum
+        if ctx.sinks is not None:                                               # inside a trainer step: += into the bucket's gradients
+            g_w, g_b, acc = ctx.sinks[0], ctx.sinks[1], True
+        else:
+            g_w, g_b, acc = torch.empty_like(weight), torch.empty_like(bias), False
+        _slab_sum([(gw_s, g_w, rows * ARS_HIDDEN, rows * ARS_HIDDEN, n, acc, 1), (gb_s, g_b, rows, rows, n, acc, 1)])
+        if acc:
+            g_w = g_b = None
+        return g_a, g_w, g_b, None, g_z, g_ld, None, None
+
+
+def ars_head(a, weight, bias, mask, z, ld, K, bound, inverse=False, col=None, out=None):
+    """the output layer of a masked-autoregressive conditioner and the rational-quadratic spline it parameterises, in one launch: for
+    row b, feature d and parameter p, ``P[p] = bias[p D + d] + sum_i a[b, i] weight[p D + d, i] mask[d, i]`` and
+    ``y[b, d] = rqs(z[b, d]; P)`` with the conventions of ``rqs_coupling``; the (B, (3K - 1) D) parameter tensor is never materialised.
+    ``a`` (B, 32) is the activated hidden layer, ``weight`` ((3K - 1) D, 32), ``bias`` ((3K - 1) D, ), ``mask`` (D, 32) of 0 / 1, ``z``
+    (B, D) with D <= 8.  Forward: every feature, ``ld`` += the log-det terms in place, autograd for ``a``, ``weight``, ``bias`` and
+    ``z`` (the direct dependence; the path through the conditioner reaches ``z`` through ``a``).  ``inverse=True`` needs ``col``: the
+    closed-form inverse of that ONE column from that feature's parameters, ``ld`` -= its term, every other column as in ``z``; it runs
+    without a graph and writes into ``out`` (default: a clone of ``z``; ``out=z`` inverts the column in place)."""
+    a, z = _contig(a), _contig(z)
+    N.ptr(z)                                                                # raises the engine's "no CPU path" error
+    K, bound = int(K), float(bound)
+    if K not in RQS_BINS:
+        raise ValueError('the spline kernels are built for %s bins, got %d' % (' / '.join(str(k) for k in RQS_BINS), K))
+    if not bound > 0.0:
+        raise ValueError('the spline interval (-bound, bound) needs bound > 0, got %r' % bound)
+    if z.dim() != 2 or not 1 <= z.shape[1] <= ARS_MAX_D:
+        raise ValueError('the autoregressive spline head takes (B, D) data with 1 <= D <= %d, got shape %s' % (ARS_MAX_D, tuple(z.shape)))
+    B, D = z.shape
+    rows = (3 * K - 1) * D
+    for name, t, want in (('hidden activations', a, (B, ARS_HIDDEN)), ('head weight', weight, (rows, ARS_HIDDEN)), ('head bias', bias, (rows, )),
+                          ('head mask', mask, (D, ARS_HIDDEN)), ('log_df_dz', ld, (B, ))):
+        if tuple(t.shape) != want:
+            raise ValueError('%s has shape %s, expected %s' % (name, tuple(t.shape), want))
+    ld = _owned_ld(ld)
+    if not inverse:
+        if col is not None or out is not None:
+            raise ValueError('col and out belong to the inverse direction (the forward transforms every feature into a new tensor)')
+        return _ARSHead.apply(a, weight, bias, mask, z, ld, K, bound)
+    if col is None or not 0 <= int(col) < D:
+        raise ValueError('the inverse takes one column per call: 0 <= col < %d, got %r' % (D, col))
+    with torch.no_grad():
+        if out is None:
+            out = z.clone()
+        elif tuple(out.shape) != (B, D):
+            raise ValueError('out has shape %s, expected %s' % (tuple(out.shape), (B, D)))
+        N.call('nf_arspline_head_fwd', N.ptr(a), N.ptr(weight), N.ptr(bias), N.ptr(mask), N.ptr(z), N.ptr(out), N.ptr(ld), K, bound, 1, int(col),
+               B, D, ARS_HIDDEN, N.stream())
+    return out, ld
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # standalone MixLogCDF (flows/modules.py:186-212)
 # ----------------------------------------------------------------------------------------------------------------------
 def _mixcdf_shapes(x, log_pi):

@@ -19,7 +19,7 @@ from . import _native as N
 from . import functional as NF
 from . import fused as FUSED
 from . import fused_flowpp_img as FPI
-from .conditioners import MLP, ConvNet, flowpp_conditioner, made_degrees_to_masks
+from .conditioners import MLP, ConvNet, flowpp_conditioner, made_degrees_to_masks, made_masks_from_degrees
 
 
 class Identity(nn.Module):
@@ -1141,3 +1141,78 @@ class AutoregressiveTransfrom(nn.Module):
             z[:, i] = cand[:, i]
             log_df_dz = log_df_dz - s
         return torch.mm(z, self.perm.t()), log_df_dz
+
+
+# ---- masked-autoregressive spline (RQ-NSF (AR), Durkan et al. 2019; no reference counterpart) ----------------------------------------
+
+class AutoregressiveSpline(nn.Module):
+    """masked autoregressive rational-quadratic spline transform: feature i of the permuted input goes through a ``bins``-piece monotone
+    spline on (-tail_bound, tail_bound) with linear tails whose 3 bins - 1 parameters are a MADE-style function of the features before it.
+    The conditioner is ``num_hidden`` masked linear layers with ReLU (no BatchNorm: the conditioner is a per-row function, so the
+    column-by-column inverse sees the same function in every pass) and a masked output layer that is fused with the spline into one
+    kernel per direction (functional.ars_head): the (B, (3 bins - 1) D) parameter tensor never exists.
+
+    The masks are FIXED at construction (hidden degrees ``arange(base_filters) % max(1, D - 1)``, registered as buffers): no draw per
+    call, so a captured training step replays the same function.  The head starts at zero: the layer starts as the identity.
+    Not a subclass of AutoregressiveTransfrom: Compose serves it through the layer's own calls."""
+
+    masks_redrawn_per_call = False
+
+    def __init__(self, in_out_features, bins=8, tail_bound=3.0, num_hidden=3, base_filters=32):
+        super().__init__()
+        D = int(in_out_features)
+        if bins not in NF.RQS_BINS:
+            raise ValueError('AutoregressiveSpline: bins must be one of %s, got %r' % (NF.RQS_BINS, bins))
+        if not float(tail_bound) > 0.0:
+            raise ValueError('AutoregressiveSpline: tail_bound must be positive, got %r' % tail_bound)
+        if not 1 <= D <= NF.ARS_MAX_D:
+            raise ValueError('AutoregressiveSpline: the fused head serves 1 <= in_out_features <= %d, got %r' % (NF.ARS_MAX_D, in_out_features))
+        if base_filters != NF.ARS_HIDDEN or num_hidden < 1:
+            raise ValueError('AutoregressiveSpline: the fused head is built for base_filters = %d and at least one hidden layer, got '
+                             'base_filters = %r, num_hidden = %r' % (NF.ARS_HIDDEN, base_filters, num_hidden))
+        self.in_out_chs, self.bins, self.tail_bound = D, int(bins), float(tail_bound)
+        self.num_hidden, self.base_filters = int(num_hidden), int(base_filters)
+        self.register_buffer('perm', torch.eye(D)[:, torch.randperm(D)])
+        masks = made_masks_from_degrees(D, self.degrees())
+        for i, m in enumerate(masks[:-1]):
+            self.register_buffer('mask%d' % i, torch.from_numpy(m))
+        self.register_buffer('head_mask', torch.from_numpy(masks[-1]))       # (D, base_filters): row d serves the 3 bins - 1 rows of feature d
+        weights, biases = [], []
+        widths = [D] + [base_filters] * num_hidden
+        for i, o in zip(widths[:-1], widths[1:]):                            # MADE's initialisation (flows/maf.py:28-33)
+            weights.append(nn.Parameter(torch.randn(o, i) * np.sqrt(2.0 / (o + i))))
+            biases.append(nn.Parameter(torch.randn(o) * 0.01))
+        self.weights = nn.ParameterList(weights)
+        self.biases = nn.ParameterList(biases)
+        self.head_weight = nn.Parameter(torch.zeros((3 * self.bins - 1) * D, base_filters))     # row p D + d: parameter p of feature d
+        self.head_bias = nn.Parameter(torch.zeros((3 * self.bins - 1) * D))
+
+    def degrees(self):
+        """the hidden units' degrees, one vector per hidden layer"""
+        return [np.arange(self.base_filters) % max(1, self.in_out_chs - 1)] * self.num_hidden
+
+    @property
+    def masks(self):
+        """[hidden masks ..., head mask (D, base_filters)]: made_masks_from_degrees(D, self.degrees())"""
+        return [getattr(self, 'mask%d' % i) for i in range(self.num_hidden)] + [self.head_mask]
+
+    def trunk(self, z):
+        """the activated last hidden layer (B, base_filters) of the permuted input; framework ops"""
+        h = z
+        for i in range(self.num_hidden):
+            h = torch.relu(F.linear(h, self.weights[i] * getattr(self, 'mask%d' % i), self.biases[i]))
+        return h
+
+    def forward(self, z, log_df_dz):
+        z = torch.mm(z, self.perm)
+        return NF.ars_head(self.trunk(z), self.head_weight, self.head_bias, self.head_mask, z, log_df_dz, self.bins, self.tail_bound)
+
+    def backward(self, z, log_df_dz):
+        """D sequential passes of trunk + head, pass i inverting column i in place in ONE clone (column i depends on the recovered
+        columns before it alone); the caller's tensor is not mutated.  No graph is built."""
+        with torch.no_grad():
+            x = z.clone()
+            for i in range(self.in_out_chs):
+                _, log_df_dz = NF.ars_head(self.trunk(x), self.head_weight, self.head_bias, self.head_mask, x, log_df_dz, self.bins,
+                                           self.tail_bound, inverse=True, col=i, out=x)
+            return torch.mm(x, self.perm.t()), log_df_dz

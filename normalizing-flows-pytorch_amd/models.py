@@ -12,7 +12,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .layers import (CNF, ActNorm, AffineCoupling, AutoregressiveTransfrom, BatchNorm, Compose, InvertibleConv1x1, Logit,
+from .layers import (CNF, ActNorm, AffineCoupling, AutoregressiveSpline, AutoregressiveTransfrom, BatchNorm, Compose, InvertibleConv1x1, Logit,
                      MixLogAttnCoupling, PlanarTransform, RQSplineCoupling, Squeeze2d, Unsqueeze2d)
 
 
@@ -235,6 +235,22 @@ class MAF(_FlowModel):
     def backward(self, z):
         self._bind_seed()
         return super().backward(z)
+
+
+class SplineMAF(_FlowModel):
+    """masked-autoregressive neural spline flow (RQ-NSF (AR) of Durkan et al. 2019; no reference counterpart): MAF's stack with the
+    affine transform replaced by AutoregressiveSpline -- [flow BatchNorm, autoregressive spline] x layers; density data only, up to eight
+    features.  cfg.bins (default 8) and cfg.tail_bound (default 3.0) are optional.  The masks are fixed, so FlowTrainer(graph=True)
+    captures the step as it is."""
+
+    def _build(self, dims, datatype, cfg):
+        if datatype == 'image':
+            raise NotImplementedError('Sorry, SplineMAF for image generation is not supported!')
+        layers = []
+        for _ in range(self.n_layers):
+            layers.append(BatchNorm(dims, affine=False))
+            layers.append(AutoregressiveSpline(dims[0], getattr(cfg, 'bins', None) or 8, getattr(cfg, 'tail_bound', None) or 3.0))
+        return layers
 
 
 class PlanarFlow(nn.Module):
