@@ -602,6 +602,17 @@ typedef struct nf_convnet_desc {
 int nf_convnet_chain_usable(int64_t B, int I0, int O_out, int H, int W);
 int nf_convnet_chain_fwd(const nf_convnet_desc* desc, int64_t B, int I0, int O_out, int H, int W, int training, float bn_eps,
                          float bn_momentum, nf_stream_t stream);
+/* A RUN of n image Glow steps of one shape (flows/glow.py:24-46: ActNorm, invertible 1 x 1, affine coupling; the conditioner of
+ * flows/modules.py:416-438; flows/coupling.py:104-122) in ONE launch: for every output and by-product the same, bit for bit, as n calls of
+ * nf_convnet_chain_fwd with descs[0], descs[1], ... in this order, in training and in evaluation mode.  1 <= n <= NF_CONVNET_RUN_MAX;
+ * n = 1 IS that call.  For n > 1 (NF_E_BADARG otherwise): a workgroup owns whole samples (no halo hand-over: 16 x 16 maps on two tiles
+ * per sample are not taken), every descriptor carries the coupling and the head (cp_z, hd_x; not cp_inverse) -- step s + 1 then reads
+ * of step s only what its own workgroup wrote, e.g. hd_x of descs[s + 1] = cp_y of descs[s] -- and cp_mode, cp_C and the presence of
+ * the packed images are the same in all of them (cp_odd may alternate).  Every descriptor keeps its own ws_zero / ws_gen, as for n
+ * launches.  The descriptors travel by value in the kernel arguments (656 bytes each).                                             */
+#define NF_CONVNET_RUN_MAX 36
+int nf_convnet_chain_fwd_run(const nf_convnet_desc* descs, int n, int64_t B, int I0, int O_out, int H, int W, int training,
+                             float bn_eps, float bn_momentum, nf_stream_t stream);
 /* The data gradient of the same conditioner in one persistent launch (the six nf_conv_bn_bwd data passes of the split form below):
  * reads the forward's by-products, writes what the deferred weight-gradient launches (nf_conv_bn_wgrad_multi) read afterwards.
  * Deterministic (the batch sums are exchanged in a fixed order, no atomics).  training == 0: the statistics are constants (no mean
@@ -649,6 +660,13 @@ typedef struct nf_convnet_bwd_desc {
 } nf_convnet_bwd_desc;
 int nf_convnet_chain_bwd(const nf_convnet_bwd_desc* desc, int64_t B, int I0, int O_out, int H, int W, int training,
                          nf_stream_t stream);
+/* The backward twin of nf_convnet_chain_fwd_run (flows/glow.py:24-46, flows/modules.py:416-438, flows/coupling.py:104-122): the same,
+ * bit for bit, as n calls of nf_convnet_chain_bwd with descs[0], descs[1], ... -- the steps in BACKWARD order, e.g. hd_g_h of
+ * descs[k + 1] = cp_g_z of descs[k].  n > 1: whole-sample tiles, the fused coupling (cp_g_y) in every descriptor, one cp_mode / cp_C /
+ * weight form, and descs[1 .. n - 1] agree on whether they carry the transposed head (descs[0], the run's last step, is free: its
+ * cp_g_y usually comes from outside the run).  cp_g_a / cp_g_c: as for n launches (ordered only in the deterministic mode).        */
+int nf_convnet_chain_bwd_run(const nf_convnet_bwd_desc* descs, int n, int64_t B, int I0, int O_out, int H, int W, int training,
+                             nf_stream_t stream);
 
 /* The chain kernels run their fp32 convolutions on the bf16 matrix pipe: every operand is split into three bf16 values (x = h + m + l
  * exactly), six of the nine partial products are accumulated in fp32 -- fp32 accuracy (measured error against float64 below that of

@@ -15,6 +15,10 @@
 //   the K splits meet in LDS, every wave finishes 16 / NKQ output channels of its pixel block: bias, residual (kept in
 //   registers: the lane that finishes (channel, pixel) of layer l also finishes it for layer l + 2), store, statistics.
 //   Batch statistics are (sum, M2) pairs merged by the parallel-variance rule: half wave -> workgroup -> grid (no E[x^2] - E[x]^2).
+//
+// A RUN of flow steps (nf_convnet_chain_fwd_run / _bwd_run): where a workgroup owns whole samples the next step of a level reads only
+// what this workgroup wrote, so the steps of a level loop INSIDE one launch -- the kernel bodies are step functions (nf_cc_fwd_step,
+// nf_cc_bwd_step) that the single-step kernels call once and the run kernels once per descriptor; see k_convnet_chain_fwd_run.
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -61,6 +65,15 @@ extern "C" int nf_cc_prof_read(long long* out) {
 #else
 #define NF_CC_STAMP(i)
 #endif
+
+// threadIdx.x as the helpers below read it.  RUN = false (the single-step kernels): the register itself.  RUN = true (a step of
+// k_convnet_chain_*_run): opaque at every read, so that nothing derived from it is hoisted out of the step loop (nf_cc_run_head)
+template <bool RUN>
+__device__ __forceinline__ unsigned nf_cc_tidx() {
+    unsigned t = threadIdx.x;
+    if (RUN) asm volatile("" : "+v"(t));
+    return t;
+}
 
 // ---- fp32 convolutions on the bf16 matrix pipe: the three-way split ------------------------------------------------------------------
 // A 32 -> 32 channel 3 x 3 layer over a 128-pixel tile is 36 x v_mfma_f32_32x32x2_f32 per wave, 3.9 us per layer with four waves per
@@ -265,12 +278,12 @@ __device__ __forceinline__ void nf_cc_pair_range(int pairs, int nkq, int kq, int
 //               (lanes run over r: contiguous in global memory for every output channel)
 // 32 * 9 * noct items (<= 1152) over 1024 threads: threads < 128 hold a second one.  Channels beyond IC load zeros.
 struct NfCcW { float v[2][8]; };
-template <bool TR>
+template <bool TR, bool RUN = false>
 __device__ __forceinline__ void nf_cc_w_load(NfCcW& w, const float* __restrict__ weight, int I, int i0, int IC, int noct) {
     const int nitems = 32 * 9 * (TR ? 4 : noct);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-        const int item = threadIdx.x + NF_CV_THREADS * t;
+        const int item = nf_cc_tidx<RUN>() + NF_CV_THREADS * t;
         if (TR) {
             const int o = item / 288, r = item - o * 288;
 #pragma unroll
@@ -284,12 +297,12 @@ __device__ __forceinline__ void nf_cc_w_load(NfCcW& w, const float* __restrict__
         }
     }
 }
-template <bool TR>
+template <bool TR, bool RUN = false>
 __device__ __forceinline__ void nf_cc_w_store(const NfCcW& w, float* W8, int WPs, int noct) {
     const int nitems = 32 * 9 * (TR ? 4 : noct);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-        const int item = threadIdx.x + NF_CV_THREADS * t;
+        const int item = nf_cc_tidx<RUN>() + NF_CV_THREADS * t;
         if (item < nitems) {
             if (TR) {
                 const int o = item / 288, r = item - o * 288, ic = r / 9, tap = r - ic * 9;
@@ -303,8 +316,9 @@ __device__ __forceinline__ void nf_cc_w_store(const NfCcW& w, float* W8, int WPs
     }
 }
 // slot `slot` of all three planes <- 0 (what the half of an odd last pair multiplies with)
+template <bool RUN = false>
 __device__ __forceinline__ void nf_cc_w_zero_slot(float* W8, int WPs, int slot) {
-    if (threadIdx.x < 3 * NF_CC_WSLOT) W8[(threadIdx.x / NF_CC_WSLOT) * WPs + slot * NF_CC_WSLOT + (threadIdx.x % NF_CC_WSLOT)] = 0.f;
+    if (nf_cc_tidx<RUN>() < 3 * NF_CC_WSLOT) W8[(nf_cc_tidx<RUN>() / NF_CC_WSLOT) * WPs + slot * NF_CC_WSLOT + (nf_cc_tidx<RUN>() % NF_CC_WSLOT)] = 0.f;
 }
 
 // K-split exchange: the NKQ waves of a pixel block each hold a partial 32 x 32 accumulator; wave kq ends up with the TOTAL of
@@ -445,8 +459,9 @@ __device__ __forceinline__ void nf_cc_half_stats(const float (&v)[OWN], bool lo_
 // gather the G x 64 published values of one exchange round into LDS (xs[workgroup][XS]: row stride 65 keeps the per-channel walks over
 // workgroups off one bank); a slot is {generation : value}, four polled per
 // trip.  A workgroup that never arrives (not co-resident, lost) ends the wait after nf_cc_spin_limit polls: sticky error word, loud on the host.
+template <bool RUN = false>
 __device__ __forceinline__ void nf_cc_collect_slots(float* xs, const unsigned long long* rs, unsigned gen, int G, int XS) {
-    for (int e0 = threadIdx.x; e0 < G * 64; e0 += 4 * NF_CV_THREADS) {
+    for (int e0 = nf_cc_tidx<RUN>(); e0 < G * 64; e0 += 4 * NF_CV_THREADS) {
         unsigned long long v[4];
         unsigned spins = 0;
         bool ok;
@@ -511,17 +526,17 @@ __device__ __forceinline__ void nf_cc_merge_rows(const float* xs, int XS, int n,
 // Returns true in the ONE lane per channel that holds the channel's totals (ci, S, M2) -- the caller finishes the BatchNorm constants
 // there and then synchronises: no barrier between the merge and the constants.  peek() runs once every row has arrived (the halo's
 // early loads).
-template <int NPB, typename Peek>
+template <int NPB, bool RUN, typename Peek>
 __device__ __forceinline__ bool nf_cc_stats_exchange(float* sm, const NfCcLds& L, unsigned long long* slots, unsigned gbase, int round,
                                                      int64_t Npx, int PXW, int& ci_out, float& S_out, float& M2_out, Peek&& peek) {
     float* red = sm + L.RED;
     float* xs = sm + L.RS;
     float* tot = sm + L.TOT;
     const int G = gridDim.x;
-    const int i = threadIdx.x & 31;
+    const int i = nf_cc_tidx<RUN>() & 31;
     __syncthreads();                                    // red complete; RS no longer read by anybody
     if (round == 1) NF_CC_STAMP(56);
-    if (threadIdx.x < 32) {
+    if (nf_cc_tidx<RUN>() < 32) {
         const int nb = nf_cc_valid_px(Npx, (int64_t)blockIdx.x * PXW, PXW);
         float S, M2;
         if (nb == PXW) {                                // every pixel block full: pairwise tree, no division
@@ -555,21 +570,21 @@ __device__ __forceinline__ bool nf_cc_stats_exchange(float* sm, const NfCcLds& L
     }
     if (G == 1) {
         peek();
-        return threadIdx.x < 32;
+        return nf_cc_tidx<RUN>() < 32;
     }
     const unsigned long long* rs = slots + (size_t)round * NF_CC_MAX_BLOCKS * 64;
     const unsigned gen = gbase + (unsigned)(round + 1);
     if (round == 1) NF_CC_STAMP(57);
 #ifdef NF_CC_PROF
-    if (round == 1 && threadIdx.x == 0) nf_cc_arrive[blockIdx.x] = wall_clock64();
+    if (round == 1 && nf_cc_tidx<RUN>() == 0) nf_cc_arrive[blockIdx.x] = wall_clock64();
 #endif
     const int XS = 65;
-    const int lane = threadIdx.x & 63, ci = 2 * (threadIdx.x >> 6) + (lane >> 5), l = lane & 31;
+    const int lane = nf_cc_tidx<RUN>() & 63, ci = 2 * (nf_cc_tidx<RUN>() >> 6) + (lane >> 5), l = lane & 31;
     float S, M2;
     if (NF_CC_MAX_BLOCKS <= NF_CC_FLAT_MAX || G <= NF_CC_FLAT_MAX) {
         // every workgroup polls every row: thread (wave w, half h, lane l) reduces channel ci = 2 w + h over the workgroups b = l,
         // l + 32, ... in a fixed order, then a butterfly over the 32 lanes
-        nf_cc_collect_slots(xs, rs, gen, G, XS);
+        nf_cc_collect_slots<RUN>(xs, rs, gen, G, XS);
         peek();
         if (round == 1) NF_CC_STAMP(58);
         __syncthreads();
@@ -583,7 +598,7 @@ __device__ __forceinline__ bool nf_cc_stats_exchange(float* sm, const NfCcLds& L
         unsigned long long* gs = slots + NF_CC_WG_SLOTS + (size_t)round * NF_CC_MAX_GROUPS * 64;
         if (blockIdx.x % NF_CC_GROUP == 0) {            // block-uniform
             const int nmem = min(NF_CC_GROUP, G - grp * NF_CC_GROUP);
-            nf_cc_collect_slots(xs, rs + (size_t)grp * NF_CC_GROUP * 64, gen, nmem, XS);
+            nf_cc_collect_slots<RUN>(xs, rs + (size_t)grp * NF_CC_GROUP * 64, gen, nmem, XS);
             __syncthreads();
             float Sg, Mg;
             nf_cc_merge_rows(xs, XS, nmem, Npx, (int64_t)grp * NF_CC_GROUP * PXW, PXW, ci, l, Sg, Mg);
@@ -595,7 +610,7 @@ __device__ __forceinline__ bool nf_cc_stats_exchange(float* sm, const NfCcLds& L
             }
             __syncthreads();                            // the group's rows are read before the gather buffer is reused
         }
-        nf_cc_collect_slots(xs, gs, gen, NG, XS);
+        nf_cc_collect_slots<RUN>(xs, gs, gen, NG, XS);
         peek();
         if (round == 1) NF_CC_STAMP(58);
         __syncthreads();
@@ -707,18 +722,18 @@ struct NfCcHeadReq {                                    // what a thread has in 
 // tile per item: the form with all row tiles of a block in registers at once (RT x 4 accumulators, RT x KQ weights, two copies of the
 // pixels) cost the WHOLE kernel ~50 spilled registers -- 1 us per launch even with the head elsewhere (round 6, same-box A/B).
 // KQ = K steps of four input channels (template parameter: the operand registers); the row tile is a run-time index.
-template <int KQ>
+template <int KQ, bool RUN = false>
 __device__ __forceinline__ void nf_cc_head_request(NfCcHeadReq& R, const nf_convnet_desc& d, const NfSplit& cs, int64_t b0, int fr_lo,
                                                    int per, int nblk, int64_t B) {
     const int C = cs.C, P = cs.H * cs.W;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
+    const int lane = nf_cc_tidx<RUN>() & 63, wid = nf_cc_tidx<RUN>() >> 6, li = lane & 15, lk = lane >> 4;
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
-        const int e = threadIdx.x + u * NF_CV_THREADS;
+        const int e = nf_cc_tidx<RUN>() + u * NF_CV_THREADS;
         R.w[u] = e < C * C ? d.hd_W[e] : 0.f;
     }
     {
-        const int c = threadIdx.x < C ? threadIdx.x : 0;
+        const int c = nf_cc_tidx<RUN>() < C ? nf_cc_tidx<RUN>() : 0;
         R.an0 = d.hd_bias[c];
         R.an1 = d.hd_ls[c];
     }
@@ -733,12 +748,12 @@ __device__ __forceinline__ void nf_cc_head_request(NfCcHeadReq& R, const nf_conv
         }
     }
 }
-template <int KQ>
+template <int KQ, bool RUN = false>
 __device__ __forceinline__ void nf_cc_head_fwd(const NfCcHeadReq& R, const nf_convnet_desc& d, const NfSplit& cs, float* hl, int64_t b0,
                                                int nsamp, int fr_lo, int fo_lo, int fo_hi, int per, int nblk, int sp0, int np1,
                                                int64_t B, bool add_ld) {
     const int C = cs.C, P = cs.H * cs.W, RT = (C + 15) >> 4;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
+    const int lane = nf_cc_tidx<RUN>() & 63, wid = nf_cc_tidx<RUN>() >> 6, li = lane & 15, lk = lane >> 4;
     float* const hout = const_cast<float*>(d.cp_z);
     float* const Ws = hl + NF_CC_HD_WS;
     float* const An = hl + NF_CC_HD_AN;
@@ -748,14 +763,14 @@ __device__ __forceinline__ void nf_cc_head_fwd(const NfCcHeadReq& R, const nf_co
         const float rc = 1.f / (float)C;               // e / C for e < 4096 by reciprocal multiplication (the half-integer offset keeps the
 #pragma unroll                                          // quotient away from every integer)
         for (int u = 0; u < 3; ++u) {
-            const int e = threadIdx.x + u * NF_CV_THREADS;
+            const int e = nf_cc_tidx<RUN>() + u * NF_CV_THREADS;
             const int er = (int)(((float)e + 0.5f) * rc);
             if (e < C * C) Ws[er * 65 + (e - er * C)] = R.w[u];
         }
     }
-    if (threadIdx.x < 64) {
-        An[threadIdx.x] = threadIdx.x < C ? R.an0 : 0.f;
-        An[64 + threadIdx.x] = threadIdx.x < C ? expf(R.an1) : 1.f;
+    if (nf_cc_tidx<RUN>() < 64) {
+        An[nf_cc_tidx<RUN>()] = nf_cc_tidx<RUN>() < C ? R.an0 : 0.f;
+        An[64 + nf_cc_tidx<RUN>()] = nf_cc_tidx<RUN>() < C ? expf(R.an1) : 1.f;
     }
     NF_CC_STAMP(108);
     if (wid == 1 && add_ld) {                           // log-det of the two layers: P (sum log_s - sum ls), one add per owned sample
@@ -839,14 +854,14 @@ __device__ __forceinline__ void nf_cc_head_fwd(const NfCcHeadReq& R, const nf_co
 // pixel with the arithmetic of the stand-alone kernel (k_glow_head_fwd<CT>, csrc/glow_head.hip: the weight assembled from its PLU factors
 // by every thread, a true division, fmaf over c ascending, the log-det term summed in channel order) -- bit-identical.  The assembled
 // weight is saved for the backward pass by thread 0 of workgroup 0 (hs_Wout).
-template <int CT>
+template <int CT, bool RUN = false>
 __device__ __forceinline__ void nf_cc_head_small_fwd(const nf_convnet_desc& d, const NfSplit& cs, float* hl, int64_t b0, int nsamp,
                                                      int fr_lo, int fr_hi, int fo_lo, int fo_hi, int sp0, int np1, int64_t B, bool add_ld) {
     const int P = cs.H * cs.W, npx = (fr_hi - fr_lo) * cs.W;
     float* const hout = const_cast<float*>(d.cp_z);
     float* const X1 = hl + NF_CC_HD_X1;
     const int lgWf = 31 - __clz(cs.W);
-    int idx = threadIdx.x, sidx = 0, p = 0;
+    int idx = nf_cc_tidx<RUN>(), sidx = 0, p = 0;
     int64_t base = 0;
     auto place = [&](int i) {
         sidx = i / npx;
@@ -868,17 +883,17 @@ __device__ __forceinline__ void nf_cc_head_small_fwd(const nf_convnet_desc& d, c
         es[c] = expf(d.hd_ls[c]);
         bb[c] = d.hd_bias[c];
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && d.hs_Wout != nullptr) {
+    if (blockIdx.x == 0 && nf_cc_tidx<RUN>() == 0 && d.hs_Wout != nullptr) {
 #pragma unroll
         for (int r = 0; r < CT; ++r)
 #pragma unroll
             for (int c = 0; c < CT; ++c) d.hs_Wout[r * CT + c] = Wm[r][c];
     }
-    if (add_ld && threadIdx.x >= NF_WAVE && threadIdx.x < NF_WAVE + nsamp && b0 + (threadIdx.x - NF_WAVE) < B) {
+    if (add_ld && nf_cc_tidx<RUN>() >= NF_WAVE && nf_cc_tidx<RUN>() < NF_WAVE + nsamp && b0 + (nf_cc_tidx<RUN>() - NF_WAVE) < B) {
         float dld = 0.f;
 #pragma unroll
         for (int c = 0; c < CT; ++c) dld += d.hd_log_s[c] - d.hd_ls[c];                       // modules.py:249, :480
-        atomicAdd(d.cp_ld + b0 + (threadIdx.x - NF_WAVE), dld * (float)P);                     // (one writer per sample: this workgroup)
+        atomicAdd(d.cp_ld + b0 + (nf_cc_tidx<RUN>() - NF_WAVE), dld * (float)P);                     // (one writer per sample: this workgroup)
     }
     while (idx < nsamp * npx) {
         if (ok) {
@@ -939,17 +954,17 @@ struct NfCcHeadBwdReq {                                 // what a thread has in 
 // Work items: (16-pixel block, row tile of 16 output channels) -- a 48-channel head on the 4 x 4 level is 8 blocks x 3 row tiles over the
 // sixteen waves, not 8 waves with three tiles each: the fp32 MFMA is the slow pipe (32 cycles per 16 x 16 x 4), four waves share a
 // SIMD's.  KQ = K steps of four input channels (a template parameter: the operand registers), the row tile is a run-time index.
-template <int KQ>
+template <int KQ, bool RUN = false>
 __device__ __forceinline__ void nf_cc_head_bwd_request(NfCcHeadBwdReq& R, const nf_convnet_bwd_desc& d, const NfSplit& cs, int64_t b0,
                                                        int fo_lo, int per, int nblk, int64_t B) {
     const int C = cs.C, P = cs.H * cs.W, RT = (C + 15) >> 4;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
+    const int lane = nf_cc_tidx<RUN>() & 63, wid = nf_cc_tidx<RUN>() >> 6, li = lane & 15, lk = lane >> 4;
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
-        const int e = threadIdx.x + u * NF_CV_THREADS;
+        const int e = nf_cc_tidx<RUN>() + u * NF_CV_THREADS;
         R.w[u] = e < C * C ? d.hd_W[e] : 0.f;
     }
-    R.ls = d.hd_ls[threadIdx.x < C ? threadIdx.x : 0];
+    R.ls = d.hd_ls[nf_cc_tidx<RUN>() < C ? nf_cc_tidx<RUN>() : 0];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int it = wid + u * NF_CV_WAVES;
@@ -966,11 +981,11 @@ __device__ __forceinline__ void nf_cc_head_bwd_request(NfCcHeadBwdReq& R, const 
 // (Carrying the results in registers to store them behind the first K loop's loads -- on gfx9 a store counts in the in-order vmcnt, so
 // later waits for loads include its acknowledgement -- measured nothing here, and eight more live registers through the launch's first
 // phase cost every launch 1.5 us in spills: the stores are issued where the values are produced.)
-template <int KQ>
+template <int KQ, bool RUN = false>
 __device__ __forceinline__ void nf_cc_head_bwd(const NfCcHeadBwdReq& R, const nf_convnet_bwd_desc& d, const NfSplit& cs, float* hl,
                                                int64_t b0, int fo_lo, int per, int nblk, int64_t B, int PXW, int HWh, int sp0) {
     const int C = cs.C, P = cs.H * cs.W, RT = (C + 15) >> 4;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
+    const int lane = nf_cc_tidx<RUN>() & 63, wid = nf_cc_tidx<RUN>() >> 6, li = lane & 15, lk = lane >> 4;
     float* const gx = const_cast<float*>(d.cp_g_y);
     float* const Ws = hl + NF_CC_HD_WS;                 // W TRANSPOSED: Ws[c][r] = W[r][c]
     float* const An = hl + NF_CC_HD_AN;
@@ -980,12 +995,12 @@ __device__ __forceinline__ void nf_cc_head_bwd(const NfCcHeadBwdReq& R, const nf
         const float rc = 1.f / (float)C;
 #pragma unroll
         for (int u = 0; u < 3; ++u) {
-            const int e = threadIdx.x + u * NF_CV_THREADS;
+            const int e = nf_cc_tidx<RUN>() + u * NF_CV_THREADS;
             const int er = (int)(((float)e + 0.5f) * rc);
             if (e < C * C) Ws[(e - er * C) * 65 + er] = R.w[u];
         }
     }
-    if (threadIdx.x < 64) An[64 + threadIdx.x] = threadIdx.x < C ? 1.f / expf(R.ls) : 1.f;
+    if (nf_cc_tidx<RUN>() < 64) An[64 + nf_cc_tidx<RUN>()] = nf_cc_tidx<RUN>() < C ? 1.f / expf(R.ls) : 1.f;
     NF_CC_STAMP(102);
     __syncthreads();
     NF_CC_STAMP(103);
@@ -1063,7 +1078,7 @@ __device__ __forceinline__ void nf_cc_head_bwd(const NfCcHeadBwdReq& R, const nf
 // The same for a head of 2 .. 4 channels (the first level of an image Glow: (3, 32, 32) under the checkerboard split): no matrix pipe,
 // a thread per pixel with the arithmetic of the stand-alone kernel (k_glow_head_bwd<CT, 1>, csrc/glow_head.hip: fmaf over r ascending, one
 // multiplication by 1 / exp(ls)) -- bit-identical.  hd_W is the weight the forward assembled from the PLU factors and saved.
-template <int CT>
+template <int CT, bool RUN = false>
 __device__ __forceinline__ void nf_cc_head_small_bwd(const nf_convnet_bwd_desc& d, const NfSplit& cs, float* hl, int64_t b0, int nsamp,
                                                      int fo_lo, int fo_hi, int64_t B, int PXW, int HWh, int sp0) {
     const int P = cs.H * cs.W, npx = (fo_hi - fo_lo) * cs.W;
@@ -1072,7 +1087,7 @@ __device__ __forceinline__ void nf_cc_head_small_bwd(const nf_convnet_bwd_desc& 
     const int lgWf = 31 - __clz(cs.W);
     // (the first pixel's operands are requested before the constants: one round trip for both)
     float G[CT];
-    int idx = threadIdx.x;
+    int idx = nf_cc_tidx<RUN>();
     auto place = [&](int i, int& sidx, int& p, int64_t& base) {
         sidx = i / npx;
         p = fo_lo * cs.W + (i - sidx * npx);
@@ -1130,11 +1145,25 @@ __device__ __forceinline__ void nf_cc_head_small_bwd(const nf_convnet_bwd_desc& 
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // (the LDS writes; see nf_cc_head_bwd)
 }
 
+// the thread's index as a step takes it: inside a run it is made opaque once per step, so that what a thread derives from it (its rows,
+// its pixel, its LDS addresses) is computed where a step needs it and not kept in registers across the whole step loop (nf_cc_run_head)
+template <bool RUN>
+__device__ __forceinline__ int nf_cc_step_tid() {
+    int tid = (int)threadIdx.x;
+    if (RUN) {
+        asm volatile("" : "+v"(tid));
+        __builtin_assume(tid >= 0 && tid < NF_CV_THREADS);
+    }
+    return tid;
+}
+
 // LDS: ONE frame F8 (three bf16 planes) | W8 (three planes; aliased by the K-split exchange and the gather buffer of the grid exchange) |
 //      kc[4][32] | kb[32] | red[2][NPB][32] | tot[64]
-template <int NPB, int NKQ, bool HALO, bool CPL, int FWc, int CSc, bool PK>
-__global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_desc d, NfCvGeo g, int I0, int O_out, int training,
-                                                                     float eps, float mom, NfSplit cs) {
+// One flow step of a launch: the whole body of k_convnet_chain_fwd, and one iteration of k_convnet_chain_fwd_run (below).  It sets up
+// every LDS region it reads (frame zero fill, X1, kb, kc, red) itself, so a caller may run it again behind nf_cc_step_end().
+template <int NPB, int NKQ, bool HALO, bool CPL, int FWc, int CSc, bool PK, bool RUN>
+__device__ __forceinline__ void nf_cc_fwd_step(const nf_convnet_desc& d, const NfCvGeo& g, int I0, int O_out, int training, float eps,
+                                               float mom, const NfSplit& cs) {
     static_assert(NPB * NKQ == NF_CV_WAVES, "sixteen waves");
     constexpr int OWN = 16 / NKQ, PXW = 32 * NPB;
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -1147,7 +1176,8 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_
     float* red = sm + L.RED;
     const int CSr = FWc > 0 ? CSc : g.CS;               // (a literal in the per-level instantiations)
     const int WPs = L.WPs;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, c32 = lane & 31, hs = lane >> 5;
+    const int tid = nf_cc_step_tid<RUN>();
+    const int lane = tid & 63, wid = tid >> 6, c32 = lane & 31, hs = lane >> 5;
     const int pb = wid % NPB, kq = wid / NPB;
     const int64_t Npx = g.B * g.HW;
     const int64_t tile = blockIdx.x;
@@ -1190,27 +1220,27 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_
     const bool hsmall = headed && cs.C <= 4;            // the thread-per-pixel form of a 2 .. 4 channel head
     NfCcHeadReq hreq;
     if (headed && !hsmall) {
-        if (cs.C <= 16) nf_cc_head_request<4>(hreq, d, cs, b0, h_rlo, h_per, h_nblk, g.B);
-        else if (cs.C <= 24) nf_cc_head_request<6>(hreq, d, cs, b0, h_rlo, h_per, h_nblk, g.B);
-        else if (cs.C <= 48) nf_cc_head_request<12>(hreq, d, cs, b0, h_rlo, h_per, h_nblk, g.B);
-        else nf_cc_head_request<16>(hreq, d, cs, b0, h_rlo, h_per, h_nblk, g.B);
+        if (cs.C <= 16) nf_cc_head_request<4, RUN>(hreq, d, cs, b0, h_rlo, h_per, h_nblk, g.B);
+        else if (cs.C <= 24) nf_cc_head_request<6, RUN>(hreq, d, cs, b0, h_rlo, h_per, h_nblk, g.B);
+        else if (cs.C <= 48) nf_cc_head_request<12, RUN>(hreq, d, cs, b0, h_rlo, h_per, h_nblk, g.B);
+        else nf_cc_head_request<16, RUN>(hreq, d, cs, b0, h_rlo, h_per, h_nblk, g.B);
     }
     NF_CC_STAMP(105);
     // ---- zero the frame (halo and padding stay zero for the whole launch) ---------------------------------------------------
-    for (int e = threadIdx.x; e < 3 * NF_CC_FP(g.CS); e += NF_CV_THREADS) sm[L.FA + e] = 0.f;
+    for (int e = nf_cc_tidx<RUN>(); e < 3 * NF_CC_FP(g.CS); e += NF_CV_THREADS) sm[L.FA + e] = 0.f;
     float* Fr = sm + L.FA;
     NF_CC_STAMP(106);
     if (hsmall) {
         const bool add_ld = !halo || y0 == 0;
-        if (cs.C == 3) nf_cc_head_small_fwd<3>(d, cs, RS, b0, h_ns, h_rlo, h_rhi, h_olo, h_ohi, h_sp0, h_np1, g.B, add_ld);
-        else if (cs.C == 4) nf_cc_head_small_fwd<4>(d, cs, RS, b0, h_ns, h_rlo, h_rhi, h_olo, h_ohi, h_sp0, h_np1, g.B, add_ld);
-        else nf_cc_head_small_fwd<2>(d, cs, RS, b0, h_ns, h_rlo, h_rhi, h_olo, h_ohi, h_sp0, h_np1, g.B, add_ld);
+        if (cs.C == 3) nf_cc_head_small_fwd<3, RUN>(d, cs, RS, b0, h_ns, h_rlo, h_rhi, h_olo, h_ohi, h_sp0, h_np1, g.B, add_ld);
+        else if (cs.C == 4) nf_cc_head_small_fwd<4, RUN>(d, cs, RS, b0, h_ns, h_rlo, h_rhi, h_olo, h_ohi, h_sp0, h_np1, g.B, add_ld);
+        else nf_cc_head_small_fwd<2, RUN>(d, cs, RS, b0, h_ns, h_rlo, h_rhi, h_olo, h_ohi, h_sp0, h_np1, g.B, add_ld);
     } else if (headed) {
         const bool add_ld = !halo || y0 == 0;
-        if (cs.C <= 16) nf_cc_head_fwd<4>(hreq, d, cs, RS, b0, h_ns, h_rlo, h_olo, h_ohi, h_per, h_nblk, h_sp0, h_np1, g.B, add_ld);
-        else if (cs.C <= 24) nf_cc_head_fwd<6>(hreq, d, cs, RS, b0, h_ns, h_rlo, h_olo, h_ohi, h_per, h_nblk, h_sp0, h_np1, g.B, add_ld);
-        else if (cs.C <= 48) nf_cc_head_fwd<12>(hreq, d, cs, RS, b0, h_ns, h_rlo, h_olo, h_ohi, h_per, h_nblk, h_sp0, h_np1, g.B, add_ld);
-        else nf_cc_head_fwd<16>(hreq, d, cs, RS, b0, h_ns, h_rlo, h_olo, h_ohi, h_per, h_nblk, h_sp0, h_np1, g.B, add_ld);
+        if (cs.C <= 16) nf_cc_head_fwd<4, RUN>(hreq, d, cs, RS, b0, h_ns, h_rlo, h_olo, h_ohi, h_per, h_nblk, h_sp0, h_np1, g.B, add_ld);
+        else if (cs.C <= 24) nf_cc_head_fwd<6, RUN>(hreq, d, cs, RS, b0, h_ns, h_rlo, h_olo, h_ohi, h_per, h_nblk, h_sp0, h_np1, g.B, add_ld);
+        else if (cs.C <= 48) nf_cc_head_fwd<12, RUN>(hreq, d, cs, RS, b0, h_ns, h_rlo, h_olo, h_ohi, h_per, h_nblk, h_sp0, h_np1, g.B, add_ld);
+        else nf_cc_head_fwd<16, RUN>(hreq, d, cs, RS, b0, h_ns, h_rlo, h_olo, h_ohi, h_per, h_nblk, h_sp0, h_np1, g.B, add_ld);
     }
     NF_CC_STAMP(107);
     if (cpl && !headed) {
@@ -1222,7 +1252,7 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_
             const int n4 = (int)(left < nsamp ? (left > 0 ? left : 0) : nsamp) * (cs.n_full >> 2);
             const float4* src = reinterpret_cast<const float4*>(d.cp_z + b0 * cs.n_full);
             float4* dst = reinterpret_cast<float4*>(d.cp_y + b0 * cs.n_full);
-            for (int idx = threadIdx.x; idx < n4; idx += NF_CV_THREADS) dst[idx] = src[idx];
+            for (int idx = nf_cc_tidx<RUN>(); idx < n4; idx += NF_CV_THREADS) dst[idx] = src[idx];
         } else if (b0 < g.B) {
             // this workgroup's share of its sample: the rows of every channel plane that its pixels map to -- one contiguous chunk of
             // PXW / HW of the plane per channel (both split maps keep conditioner rows in order)
@@ -1230,7 +1260,7 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_
             const int part = (int)((tile * PXW) & (g.HW - 1)) / PXW;
             const float4* src = reinterpret_cast<const float4*>(d.cp_z + b0 * cs.n_full);
             float4* dst = reinterpret_cast<float4*>(d.cp_y + b0 * cs.n_full);
-            for (int idx = threadIdx.x; idx < cs.C * chunk4; idx += NF_CV_THREADS) {
+            for (int idx = nf_cc_tidx<RUN>(); idx < cs.C * chunk4; idx += NF_CV_THREADS) {
                 const int c = idx / chunk4, r = idx - c * chunk4;
                 dst[c * plane4 + part * chunk4 + r] = src[c * plane4 + part * chunk4 + r];
             }
@@ -1251,17 +1281,17 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_
         for (int ch = 0; ch < nchunks; ++ch) {
             const int i0 = 32 * ch, IC = min(32, I0 - i0), ICP = (IC + 7) & ~7, noct = ICP >> 3;
             NfCcW wv;
-            if (!packed) nf_cc_w_load<false>(wv, d.w[0], I0, i0, IC, noct);
+            if (!packed) nf_cc_w_load<false, RUN>(wv, d.w[0], I0, i0, IC, noct);
             __syncthreads();                            // the previous chunk's readers of Wl / the frame are done (and the zero fill)
             if (packed) {
                 nf_cc_dma_image(Wl, d.wpk[0] + (size_t)ch * NF_CONV_PACK_IMAGE_FLOATS, wid, lane);   // lands under the frame staging
             } else {
-                nf_cc_w_store<false>(wv, Wl, WPs, noct);
-                if ((9 * noct) & 1) nf_cc_w_zero_slot(Wl, WPs, 9 * noct);
+                nf_cc_w_store<false, RUN>(wv, Wl, WPs, noct);
+                if ((9 * noct) & 1) nf_cc_w_zero_slot<RUN>(Wl, WPs, 9 * noct);
             }
             // the chunk's input frame as ITEMS: the eight channels of octet o at frame position f -- eight loads in flight per item (one
             // memory round trip per chunk), a split, three 16-byte stores (a position outside the image / batch stores zeros)
-            for (int item = threadIdx.x; item < noct * g.FSZ; item += NF_CV_THREADS) {
+            for (int item = nf_cc_tidx<RUN>(); item < noct * g.FSZ; item += NF_CV_THREADS) {
                 const int o = item / g.FSZ, f = item - o * g.FSZ;
                 const int t = nf_cv_decode(g, b0, y0, f);
                 const int sp = t >= 0 ? NF_CV_SP(t) : 0, sg_ = t >= 0 ? NF_CV_SEG(t) : 0;
@@ -1293,14 +1323,14 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_
     // bias, gamma, beta of a layer are loaded by threads < 32 BEFORE the K loop that precedes their use (a global load at the point of
     // use is ~0.7 us of exposed latency on the serial chain, twice per layer)
     float nb_ = 0.f, ng_ = 0.f, nbe_ = 0.f;
-    if (threadIdx.x < 32) { nb_ = d.b[0][threadIdx.x]; ng_ = d.gamma[0][threadIdx.x]; nbe_ = d.beta[0][threadIdx.x]; }
+    if (nf_cc_tidx<RUN>() < 32) { nb_ = d.b[0][nf_cc_tidx<RUN>()]; ng_ = d.gamma[0][nf_cc_tidx<RUN>()]; nbe_ = d.beta[0][nf_cc_tidx<RUN>()]; }
 #pragma unroll 1
     for (int l = 0; l < NF_CC_NB; ++l) {
         // next layer's 32 x 32 x 9 weights: loads in flight under the exchanges of this layer
         constexpr bool PREFETCH_W = OWN <= 4;           // OWN = 8 has no registers to spare: it loads at the point of use
         NfCcW wv;
-        if (!packed && PREFETCH_W && l < NF_CC_NB - 1) nf_cc_w_load<false>(wv, d.w[l + 1], 32, 0, 32, 4);
-        if (threadIdx.x < 32) { kb[threadIdx.x] = nb_; kb[32 + threadIdx.x] = ng_; kb[64 + threadIdx.x] = nbe_; }
+        if (!packed && PREFETCH_W && l < NF_CC_NB - 1) nf_cc_w_load<false, RUN>(wv, d.w[l + 1], 32, 0, 32, 4);
+        if (nf_cc_tidx<RUN>() < 32) { kb[nf_cc_tidx<RUN>()] = nb_; kb[32 + nf_cc_tidx<RUN>()] = ng_; kb[64 + nf_cc_tidx<RUN>()] = nbe_; }
         __syncthreads();                                // every wave is done with Wl / the frame of this layer; kb is written
         // the next layer's weight image streams into Wl under this layer's exchanges (the 1 x 1's under the last layer's)
         if (packed && (l < NF_CC_NB - 1 || cpl)) nf_cc_dma_image(Wl, d.wpk[l + 1], wid, lane);   // (the 1 x 1 image has the coupling's row order)
@@ -1334,7 +1364,7 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_
         if (training) {
             int k;
             float tS, tM2;
-            const bool fin = nf_cc_stats_exchange<NPB>(sm, L, slots, gbase, l, Npx, PXW, k, tS, tM2, [&] {
+            const bool fin = nf_cc_stats_exchange<NPB, RUN>(sm, L, slots, gbase, l, Npx, PXW, k, tS, tM2, [&] {
                 if (halo) nf_cc_halo_peek(hw, hslots, l, g, (int)tile, y0);
             });
             NF_CC_STAMP(5 + 8 * l);
@@ -1357,8 +1387,8 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_
             }
         } else {
             __syncthreads();                            // RS readers done before the frames are written
-            if (threadIdx.x < 32) {
-                const int k = threadIdx.x;
+            if (nf_cc_tidx<RUN>() < 32) {
+                const int k = nf_cc_tidx<RUN>();
                 const float mean = d.rmean[l][k], invstd = 1.f / sqrtf(d.rvar[l][k] + eps);
                 const float sc = kb[32 + k] * invstd;
                 kc[k] = sc;
@@ -1392,8 +1422,8 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_
             nf_cc_frame_store2(Fr, CSr, c0, fpos, pv ? fmaxf(fmaf(own[0], kc[c0], kc[32 + c0]), 0.f) : 0.f,
                                pv ? fmaxf(fmaf(own[1], kc[c0 + 1], kc[32 + c0 + 1]), 0.f) : 0.f);
         }
-        if (halo && threadIdx.x < 32 * g.W) {           // the neighbours' boundary rows, normalised like our own pixels
-            const int c = threadIdx.x >> g.lgW;
+        if (halo && nf_cc_tidx<RUN>() < 32 * g.W) {           // the neighbours' boundary rows, normalised like our own pixels
+            const int c = nf_cc_tidx<RUN>() >> g.lgW;
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 float v = 0.f;
@@ -1402,10 +1432,10 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_
             }
         }
         if (l < NF_CC_NB - 1) {
-            if (threadIdx.x < 32) { nb_ = d.b[l + 1][threadIdx.x]; ng_ = d.gamma[l + 1][threadIdx.x]; nbe_ = d.beta[l + 1][threadIdx.x]; }
+            if (nf_cc_tidx<RUN>() < 32) { nb_ = d.b[l + 1][nf_cc_tidx<RUN>()]; ng_ = d.gamma[l + 1][nf_cc_tidx<RUN>()]; nbe_ = d.beta[l + 1][nf_cc_tidx<RUN>()]; }
             if (!packed) {
-                if (!PREFETCH_W) nf_cc_w_load<false>(wv, d.w[l + 1], 32, 0, 32, 4);
-                nf_cc_w_store<false>(wv, Wl, WPs, 4);
+                if (!PREFETCH_W) nf_cc_w_load<false, RUN>(wv, d.w[l + 1], 32, 0, 32, 4);
+                nf_cc_w_store<false, RUN>(wv, Wl, WPs, 4);
             } else {
                 nf_cc_dma_wait();
             }
@@ -1435,7 +1465,7 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_
     const int Ch = O_out >> 1;
     const bool packed5 = packed && cpl;                 // the packed 1 x 1 image has the row order of the fused coupling
     if (packed5) nf_cc_dma_wait();
-    for (int e = threadIdx.x; e < (packed5 ? 0 : 32 * OCB * 4); e += NF_CV_THREADS) {
+    for (int e = nf_cc_tidx<RUN>(); e < (packed5 ? 0 : 32 * OCB * 4); e += NF_CV_THREADS) {
         const int row = e >> 2, o = e & 3;              // staged row -> the output channel it holds; octet o of its 32 input channels
         int oc = row;
         if (cpl) {
@@ -1488,22 +1518,22 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_
         __syncthreads();
         RS[(kq * 2 + hs) * PXW + px] = ls;
         __syncthreads();
-        if (threadIdx.x < PXW) {
+        if (nf_cc_tidx<RUN>() < PXW) {
             float v = 0.f;
 #pragma unroll
-            for (int k = 0; k < 2 * NKQ; ++k) v += RS[k * PXW + threadIdx.x];
+            for (int k = 0; k < 2 * NKQ; ++k) v += RS[k * PXW + nf_cc_tidx<RUN>()];
             const int seg = g.HW < NF_WAVE ? g.HW : NF_WAVE;
             for (int off = seg >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, NF_WAVE);
             if (g.HW <= NF_WAVE) {
-                const int64_t bb = b0 + ((int)threadIdx.x >> g.lgHW);
-                if ((threadIdx.x & (g.HW - 1)) == 0 && bb < g.B) atomicAdd(d.cp_ld + bb, d.cp_inverse ? -v : v);   // (no return value: nothing waits)
+                const int64_t bb = b0 + ((int)nf_cc_tidx<RUN>() >> g.lgHW);
+                if ((nf_cc_tidx<RUN>() & (g.HW - 1)) == 0 && bb < g.B) atomicAdd(d.cp_ld + bb, d.cp_inverse ? -v : v);   // (no return value: nothing waits)
             } else if (lane == 0) {
                 red[wid] = v;
             }
         }
         if (g.HW > NF_WAVE) {                           // block-uniform: one sample per workgroup
             __syncthreads();
-            if (threadIdx.x == 0 && b0 < g.B) {
+            if (nf_cc_tidx<RUN>() == 0 && b0 < g.B) {
                 float v = 0.f;
                 for (int k = 0; k < (min(g.HW, PXW) >> 6); ++k) v += red[k];
                 if (halo) {
@@ -1536,6 +1566,63 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_
         }
     }
     NF_CC_STAMP(51);
+}
+
+template <int NPB, int NKQ, bool HALO, bool CPL, int FWc, int CSc, bool PK>
+__global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd(nf_convnet_desc d, NfCvGeo g, int I0, int O_out, int training,
+                                                                     float eps, float mom, NfSplit cs) {
+    nf_cc_fwd_step<NPB, NKQ, HALO, CPL, FWc, CSc, PK, false>(d, g, I0, O_out, training, eps, mom, cs);
+}
+
+// ---- a RUN of flow steps in one launch (nf_convnet_chain_fwd_run / _bwd_run) -----------------------------------------------------------
+// Whole-sample tiles only (HALO = false), coupling and head in the launch: step s + 1 then reads nothing of step s but what its OWN
+// workgroup wrote (forward: the head reads cp_y of step s for the workgroup's samples; backward: the transposed head reads cp_g_z of the
+// step behind it), and the only traffic between workgroups stays the BatchNorm exchanges.  So the step boundary is a workgroup matter:
+// every thread waits for its global stores and its no-return log-det adds (vmcnt counts both), a workgroup barrier follows, and the next
+// step's prologue reads the values back through the compute unit's own L1, which the stores wrote through -- no agent-scope fence
+// (~20 us).
+// Exchange slots: every step keeps its own ws_gen, i.e. its own tags.  The row of exchange round l is rewritten by its owner only five
+// exchanges later (round l of the next step), and the owner gets there only after every workgroup has published rounds l + 1 .. 4 of this
+// step and 0 .. l - 1 of the next -- each of which a workgroup publishes after it has COLLECTED the round before.  A waiting workgroup
+// therefore lags its peers by at most one exchange and never meets a later tag in a row it still polls; the spin limit and the give-up
+// path are those of the single-step kernels.
+__device__ __forceinline__ void nf_cc_step_end() {
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+}
+// The step loop must not look like one to the optimiser: every index a thread derives from the geometry and the split map is invariant
+// over the steps, gets hoisted in front of the loop and is kept in (and spilled from) VGPRs for the whole launch -- the first form of
+// these kernels spilled 260 (forward) and 430 (backward) registers per lane where the single-step kernels spill about 10.  So the
+// launch-uniform arguments travel as ONE struct, the FIRST kernel argument (offset 0 of the kernel-argument segment), and every step
+// reads them again through a pointer that an empty asm makes opaque (scalar loads, a few per step); the thread index likewise
+// (nf_cc_step_tid).
+struct NfCcRunHead {
+    NfCvGeo g;
+    NfSplit cs;
+    int n, I0, O_out, training;
+    float eps, mom;
+};
+struct NfCcRunArgs { nf_convnet_desc d[NF_CONVNET_RUN_MAX]; };
+struct NfCcRunBwdArgs { nf_convnet_bwd_desc d[NF_CONVNET_RUN_MAX]; };
+__device__ __forceinline__ void nf_cc_run_head(NfCcRunHead& h) {
+    int z = 0;                                          // an offset of zero that the optimiser cannot see through, wave-uniform
+    asm volatile("" : "+s"(z));
+    z = __builtin_amdgcn_readfirstlane(z);
+    typedef const __attribute__((address_space(4))) NfCcRunHead* HeadPtr;      // (constant address space, aligned: scalar loads)
+    const HeadPtr p = (HeadPtr)((unsigned long long)__builtin_amdgcn_kernarg_segment_ptr() + (unsigned)z);
+    __builtin_memcpy(&h, p, sizeof(NfCcRunHead));
+}
+
+template <int NPB, int NKQ, int FWc, int CSc, bool PK>
+__global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_fwd_run(NfCcRunHead h0, NfCcRunArgs a) {
+#pragma unroll 1
+    for (int s = 0; s < h0.n; ++s) {
+        NfCcRunHead h;
+        nf_cc_run_head(h);
+        h.cs.odd = a.d[s].cp_odd ? 1 : 0;               // (one split map per run but for the side: consecutive couplings alternate it)
+        nf_cc_fwd_step<NPB, NKQ, false, true, FWc, CSc, PK, true>(a.d[s], h.g, h.I0, h.O_out, h.training, h.eps, h.mom, h.cs);
+        nf_cc_step_end();
+    }
 }
 
 // =====================================================================================================================================
@@ -1614,7 +1701,7 @@ __device__ __forceinline__ void nf_cc_half_sums2(const float (&u)[OWN], const fl
 }
 
 // grid-wide plain sums of 2 x 32 values: red[h][pb][c] -> tot[32 h + c]; fixed summation order.  peek(): as in nf_cc_stats_exchange
-template <int NPB, typename Peek>
+template <int NPB, bool RUN, typename Peek>
 __device__ __forceinline__ const float* nf_cc_sum_exchange(float* sm, const NfCcLds& L, unsigned long long* slots, unsigned gbase, int round,
                                                            Peek&& peek) {
     float* red = sm + L.RED;
@@ -1622,8 +1709,8 @@ __device__ __forceinline__ const float* nf_cc_sum_exchange(float* sm, const NfCc
     float* tot = sm + L.TOT;
     const int G = gridDim.x;
     __syncthreads();                                    // red complete; RS / Wl no longer read by anybody
-    if (threadIdx.x < 64) {
-        const int i = threadIdx.x & 31, h = threadIdx.x >> 5;
+    if (nf_cc_tidx<RUN>() < 64) {
+        const int i = nf_cc_tidx<RUN>() & 31, h = nf_cc_tidx<RUN>() >> 5;
         float sv[NPB];
 #pragma unroll
         for (int q = 0; q < NPB; ++q) sv[q] = red[(h * NPB + q) * 32 + i];
@@ -1631,9 +1718,9 @@ __device__ __forceinline__ const float* nf_cc_sum_exchange(float* sm, const NfCc
         for (int w = 1; w < NPB; w *= 2)
 #pragma unroll
             for (int q = 0; q < NPB; q += 2 * w) sv[q] += sv[q + w];
-        if (G == 1) tot[threadIdx.x] = sv[0];
+        if (G == 1) tot[nf_cc_tidx<RUN>()] = sv[0];
         else
-            __hip_atomic_store(slots + ((size_t)round * NF_CC_MAX_BLOCKS + blockIdx.x) * 64 + threadIdx.x,
+            __hip_atomic_store(slots + ((size_t)round * NF_CC_MAX_BLOCKS + blockIdx.x) * 64 + nf_cc_tidx<RUN>(),
                                ((unsigned long long)(gbase + round + 1) << 32) | (unsigned long long)__float_as_uint(sv[0]), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -1645,14 +1732,14 @@ __device__ __forceinline__ const float* nf_cc_sum_exchange(float* sm, const NfCc
     const int XS = 65;
     const unsigned gen = gbase + (unsigned)(round + 1);
     const unsigned long long* rs = slots + (size_t)round * NF_CC_MAX_BLOCKS * 64;
-    const int lane = threadIdx.x & 63, ci = 2 * (threadIdx.x >> 6) + (lane >> 5), l = lane & 31;
+    const int lane = nf_cc_tidx<RUN>() & 63, ci = 2 * (nf_cc_tidx<RUN>() >> 6) + (lane >> 5), l = lane & 31;
     int nrows = G;
     if (NF_CC_MAX_BLOCKS > NF_CC_FLAT_MAX && G > NF_CC_FLAT_MAX) {     // two levels, as in the forward kernel's statistics exchange
         const int grp = blockIdx.x / NF_CC_GROUP;
         unsigned long long* gs = slots + NF_CC_WG_SLOTS + (size_t)round * NF_CC_MAX_GROUPS * 64;
         if (blockIdx.x % NF_CC_GROUP == 0) {
             const int nmem = min(NF_CC_GROUP, G - grp * NF_CC_GROUP);
-            nf_cc_collect_slots(xs, rs + (size_t)grp * NF_CC_GROUP * 64, gen, nmem, XS);
+            nf_cc_collect_slots<RUN>(xs, rs + (size_t)grp * NF_CC_GROUP * 64, gen, nmem, XS);
             __syncthreads();
             float pa = 0.f, pb = 0.f;
             for (int b = l; b < nmem; b += 32) { pa += xs[b * XS + ci]; pb += xs[b * XS + 32 + ci]; }
@@ -1668,7 +1755,7 @@ __device__ __forceinline__ const float* nf_cc_sum_exchange(float* sm, const NfCc
         rs = gs;
         nrows = (G + NF_CC_GROUP - 1) / NF_CC_GROUP;
     }
-    nf_cc_collect_slots(xs, rs, gen, nrows, XS);
+    nf_cc_collect_slots<RUN>(xs, rs, gen, nrows, XS);
     peek();
     __syncthreads();
     {
@@ -1681,9 +1768,10 @@ __device__ __forceinline__ const float* nf_cc_sum_exchange(float* sm, const NfCc
     return tot;
 }
 
-template <int NPB, int NKQ, bool HALO, bool CPL, int FWc, int CSc, bool PK>
-__global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_bwd_desc d, NfCvGeo g, int I0, int O_out, int training,
-                                                                     NfSplit cs) {
+// (one flow step of a launch, as nf_cc_fwd_step; RUN: an iteration of k_convnet_chain_bwd_run)
+template <int NPB, int NKQ, bool HALO, bool CPL, int FWc, int CSc, bool PK, bool RUN>
+__device__ __forceinline__ void nf_cc_bwd_step(const nf_convnet_bwd_desc& d, const NfCvGeo& g, int I0, int O_out, int training,
+                                               const NfSplit& cs) {
     static_assert(NPB * NKQ == NF_CV_WAVES, "sixteen waves");
     constexpr int OWN = 16 / NKQ, PXW = 32 * NPB;
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -1694,7 +1782,8 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
     float* red = sm + L.RED;
     const int CSr = FWc > 0 ? CSc : g.CS;               // (a literal in the per-level instantiations)
     const int WPs = L.WPs;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, c32 = lane & 31, hs = lane >> 5;
+    const int tid = nf_cc_step_tid<RUN>();
+    const int lane = tid & 63, wid = tid >> 6, c32 = lane & 31, hs = lane >> 5;
     const int pb = wid % NPB, kq = wid / NPB;
     const int64_t Npx = g.B * g.HW;
     const int64_t tile = blockIdx.x;
@@ -1723,21 +1812,21 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
     NfCcHeadBwdReq hbreq;
     const bool hbs = hbw && cs.C <= 4;                  // the thread-per-pixel form of a 2 .. 4 channel head
     if (hbw && !hbs) {
-        if (cs.C <= 16) nf_cc_head_bwd_request<4>(hbreq, d, cs, b0, hb_lo, hb_per, hb_nblk, g.B);
-        else if (cs.C <= 24) nf_cc_head_bwd_request<6>(hbreq, d, cs, b0, hb_lo, hb_per, hb_nblk, g.B);
-        else if (cs.C <= 48) nf_cc_head_bwd_request<12>(hbreq, d, cs, b0, hb_lo, hb_per, hb_nblk, g.B);
-        else nf_cc_head_bwd_request<16>(hbreq, d, cs, b0, hb_lo, hb_per, hb_nblk, g.B);
+        if (cs.C <= 16) nf_cc_head_bwd_request<4, RUN>(hbreq, d, cs, b0, hb_lo, hb_per, hb_nblk, g.B);
+        else if (cs.C <= 24) nf_cc_head_bwd_request<6, RUN>(hbreq, d, cs, b0, hb_lo, hb_per, hb_nblk, g.B);
+        else if (cs.C <= 48) nf_cc_head_bwd_request<12, RUN>(hbreq, d, cs, b0, hb_lo, hb_per, hb_nblk, g.B);
+        else nf_cc_head_bwd_request<16, RUN>(hbreq, d, cs, b0, hb_lo, hb_per, hb_nblk, g.B);
     }
-    for (int e = threadIdx.x; e < 3 * NF_CC_FP(g.CS); e += NF_CV_THREADS) sm[L.FA + e] = 0.f;
+    for (int e = nf_cc_tidx<RUN>(); e < 3 * NF_CC_FP(g.CS); e += NF_CV_THREADS) sm[L.FA + e] = 0.f;
     float* Fr = sm + L.FA;                              // ONE frame: G_l is written over G_{l+1} after every wave has left the K loop
     const bool bnv = L.BNV >= 0;                        // block-uniform
     constexpr bool packed = PK;                         // compile-time: transposed weight images (nf_conv_weight_pack)
     const int nch0 = (I0 + 31) / 32;                    // a 3 x 3 layer's buffer: its forward images, then the transposed ones
     if (packed) nf_cc_dma_image(Wl, d.wpk[5] + NF_CONV_PACK_IMAGE_FLOATS, wid, lane);
-    if (bnv && threadIdx.x < NF_CC_NB * 128) {          // [layer][mean | invstd | gamma | beta][32]; first read after the barrier below
-        const int l2 = threadIdx.x >> 7, j = (threadIdx.x >> 5) & 3, k = threadIdx.x & 31;
+    if (bnv && nf_cc_tidx<RUN>() < NF_CC_NB * 128) {          // [layer][mean | invstd | gamma | beta][32]; first read after the barrier below
+        const int l2 = nf_cc_tidx<RUN>() >> 7, j = (nf_cc_tidx<RUN>() >> 5) & 3, k = nf_cc_tidx<RUN>() & 31;
         const float* src = j == 0 ? d.save_mean[l2] : (j == 1 ? d.save_invstd[l2] : (j == 2 ? d.gamma[l2] : d.beta[l2]));
-        sm[L.BNV + threadIdx.x] = src[k];
+        sm[L.BNV + nf_cc_tidx<RUN>()] = src[k];
     }
 
     // ---- the 1 x 1 output convolution, transposed: acc[ic][pixel] = sum_oc W5[oc][ic] g_out[oc][pixel].  No halo: the B operand comes
@@ -1746,15 +1835,15 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
     NF_CC_STAMP(100);
     if (hbs) {
         const int hb_sp0 = halo ? y0 * g.W : 0;
-        if (cs.C == 3) nf_cc_head_small_bwd<3>(d, cs, RS, b0, hb_ns, hb_lo, hb_hi, g.B, PXW, g.HW, hb_sp0);
-        else if (cs.C == 4) nf_cc_head_small_bwd<4>(d, cs, RS, b0, hb_ns, hb_lo, hb_hi, g.B, PXW, g.HW, hb_sp0);
-        else nf_cc_head_small_bwd<2>(d, cs, RS, b0, hb_ns, hb_lo, hb_hi, g.B, PXW, g.HW, hb_sp0);
+        if (cs.C == 3) nf_cc_head_small_bwd<3, RUN>(d, cs, RS, b0, hb_ns, hb_lo, hb_hi, g.B, PXW, g.HW, hb_sp0);
+        else if (cs.C == 4) nf_cc_head_small_bwd<4, RUN>(d, cs, RS, b0, hb_ns, hb_lo, hb_hi, g.B, PXW, g.HW, hb_sp0);
+        else nf_cc_head_small_bwd<2, RUN>(d, cs, RS, b0, hb_ns, hb_lo, hb_hi, g.B, PXW, g.HW, hb_sp0);
     } else if (hbw) {                                   // (the weight image and the BatchNorm vectors requested above are in flight)
         const int hb_sp0 = halo ? y0 * g.W : 0;
-        if (cs.C <= 16) nf_cc_head_bwd<4>(hbreq, d, cs, RS, b0, hb_lo, hb_per, hb_nblk, g.B, PXW, g.HW, hb_sp0);
-        else if (cs.C <= 24) nf_cc_head_bwd<6>(hbreq, d, cs, RS, b0, hb_lo, hb_per, hb_nblk, g.B, PXW, g.HW, hb_sp0);
-        else if (cs.C <= 48) nf_cc_head_bwd<12>(hbreq, d, cs, RS, b0, hb_lo, hb_per, hb_nblk, g.B, PXW, g.HW, hb_sp0);
-        else nf_cc_head_bwd<16>(hbreq, d, cs, RS, b0, hb_lo, hb_per, hb_nblk, g.B, PXW, g.HW, hb_sp0);
+        if (cs.C <= 16) nf_cc_head_bwd<4, RUN>(hbreq, d, cs, RS, b0, hb_lo, hb_per, hb_nblk, g.B, PXW, g.HW, hb_sp0);
+        else if (cs.C <= 24) nf_cc_head_bwd<6, RUN>(hbreq, d, cs, RS, b0, hb_lo, hb_per, hb_nblk, g.B, PXW, g.HW, hb_sp0);
+        else if (cs.C <= 48) nf_cc_head_bwd<12, RUN>(hbreq, d, cs, RS, b0, hb_lo, hb_per, hb_nblk, g.B, PXW, g.HW, hb_sp0);
+        else nf_cc_head_bwd<16, RUN>(hbreq, d, cs, RS, b0, hb_lo, hb_per, hb_nblk, g.B, PXW, g.HW, hb_sp0);
     }
     NF_CC_STAMP(101);
     const int Ch = O_out >> 1;
@@ -1767,7 +1856,7 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
     {
         const int npair = (O_out + 15) >> 4;            // pairs of octets of the K axis (= output channels of the 1 x 1)
         if (packed) nf_cc_dma_wait();
-        for (int e = threadIdx.x; e < (packed ? 0 : npair * 2 * 32); e += NF_CV_THREADS) {
+        for (int e = nf_cc_tidx<RUN>(); e < (packed ? 0 : npair * 2 * 32); e += NF_CV_THREADS) {
             const int o = e >> 5, ic = e & 31;          // W8T[plane][octet o of the output channel][ic][oc & 7]
             float v[8];
 #pragma unroll
@@ -1839,8 +1928,8 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
 #pragma unroll 1
     for (int l = NF_CC_NB - 1; l >= 0; --l) {
         // BatchNorm l (input of the convolution whose transpose just ran): scale / shift exactly as the forward kernel computed them
-        if (threadIdx.x < 32) {
-            const int k = threadIdx.x;
+        if (nf_cc_tidx<RUN>() < 32) {
+            const int k = nf_cc_tidx<RUN>();
             const float* v = sm + L.BNV + 128 * l;
             const float mean = bnv ? v[k] : d.save_mean[l][k], invstd = bnv ? v[32 + k] : d.save_invstd[l][k];
             const float sc = (bnv ? v[64 + k] : d.gamma[l][k]) * invstd;
@@ -1859,8 +1948,8 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
             }
         }
         float a_h[2] = {0.f, 0.f};                      // forward activations at our halo pixels (threads < 32 W; loads in flight early)
-        if (halo && threadIdx.x < 32 * g.W) {
-            const int c = threadIdx.x >> g.lgW, x = threadIdx.x & (g.W - 1);
+        if (halo && nf_cc_tidx<RUN>() < 32 * g.W) {
+            const int c = nf_cc_tidx<RUN>() >> g.lgW, x = nf_cc_tidx<RUN>() & (g.W - 1);
             if (y0 > 0) a_h[0] = d.acts[l][(b0 * 32 + c) * g.HW + (y0 - 1) * g.W + x];
             if (y0 + g.TH < g.H) a_h[1] = d.acts[l][(b0 * 32 + c) * g.HW + (y0 + g.TH) * g.W + x];
         }
@@ -1871,7 +1960,7 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
             else if (d.g_x != nullptr || cpl) nf_cc_dma_image(Wl, d.wpk[0] + (size_t)nch0 * NF_CONV_PACK_IMAGE_FLOATS, wid, lane);
         }
         NF_CC_STAMP(66 + 6 * (4 - l));
-        if (cpl && l == NF_CC_NB - 1 && threadIdx.x == 0) {
+        if (cpl && l == NF_CC_NB - 1 && nf_cc_tidx<RUN>() == 0) {
             float ta = 0.f, tc = 0.f;
             for (int k = 0; k < NF_CV_WAVES; ++k) { ta += red[k]; tc += red[NF_CV_WAVES + k]; }
             // (deterministic mode: the workgroups add in block order.  Safe inside the persistent loop: a workgroup with a smaller
@@ -1887,6 +1976,9 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
                     atomicAdd(d.cp_g_c, tc);
                     nf_det_pass(nf_ccd_det);
                 }
+                // (a run: the fold's counter and slab are reused by the next step -- the last workgroup's reset has been performed
+                //  before this thread takes part in the exchange that lets anybody get there)
+                if (RUN) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             } else {
                 atomicAdd(d.cp_g_a, ta);
                 atomicAdd(d.cp_g_c, tc);
@@ -1921,15 +2013,15 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
                 red[pb * 32 + oc] = S1;
                 red[NPB * 32 + pb * 32 + oc] = S2;
             }
-            tot = nf_cc_sum_exchange<NPB>(sm, L, slots, gbase, l, [&] {
+            tot = nf_cc_sum_exchange<NPB, RUN>(sm, L, slots, gbase, l, [&] {
                 if (halo) nf_cc_halo_peek(hw, hslots, l, g, (int)tile, y0);
             });
             NF_CC_STAMP(68 + 6 * (4 - l));
-            if (blockIdx.x == 0 && threadIdx.x < 64) {
-                (threadIdx.x < 32 ? d.sum_g[l] : d.sum_gx[l])[threadIdx.x & 31] = tot[threadIdx.x];
+            if (blockIdx.x == 0 && nf_cc_tidx<RUN>() < 64) {
+                (nf_cc_tidx<RUN>() < 32 ? d.sum_g[l] : d.sum_gx[l])[nf_cc_tidx<RUN>() & 31] = tot[nf_cc_tidx<RUN>()];
                 // the sums ARE the gradients of beta (sum gn) and gamma (sum gn xhat): straight into the caller's accumulators
-                float* sink = threadIdx.x < 32 ? d.g_beta[l] : d.g_gamma[l];
-                if (sink != nullptr) sink[threadIdx.x & 31] += tot[threadIdx.x];
+                float* sink = nf_cc_tidx<RUN>() < 32 ? d.g_beta[l] : d.g_gamma[l];
+                if (sink != nullptr) sink[nf_cc_tidx<RUN>() & 31] += tot[nf_cc_tidx<RUN>()];
             }
 #pragma unroll
             for (int rr = 0; rr < OWN; ++rr) {
@@ -1958,8 +2050,8 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
         }
         if constexpr (OWN == 2) nf_cc_frame_store2(Fr, CSr, nf_cv_cd_row(OWN * kq, hs), fpos, own[0], own[1]);
         if constexpr (OWN == 1) nf_cc_frame_store1(Fr, CSr, nf_cv_cd_row(kq, hs), fpos, own[0]);
-        if (halo && threadIdx.x < 32 * g.W) {           // G_l at the neighbours' boundary rows: the same per-pixel formula, their gn
-            const int c = threadIdx.x >> g.lgW;
+        if (halo && nf_cc_tidx<RUN>() < 32 * g.W) {           // G_l at the neighbours' boundary rows: the same per-pixel formula, their gn
+            const int c = nf_cc_tidx<RUN>() >> g.lgW;
             const float mgc = training ? tot[c] * invN : 0.f, mgxc = training ? tot[32 + c] * invN : 0.f;
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
@@ -1977,8 +2069,8 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
         if (l >= 1) {                                   // transposed 3 x 3 convolution l: G_l -> layer l - 1
             if (!packed) {
                 NfCcW wv;
-                nf_cc_w_load<true>(wv, d.w[l], 32, 0, 32, 4);
-                nf_cc_w_store<true>(wv, Wl, WPs, 4);
+                nf_cc_w_load<true, RUN>(wv, d.w[l], 32, 0, 32, 4);
+                nf_cc_w_store<true, RUN>(wv, Wl, WPs, 4);
             } else {
                 nf_cc_dma_wait();
             }
@@ -2004,9 +2096,9 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
             const int IC = min(32, I0 - i0);
             if (!packed) {
                 NfCcW wv;
-                nf_cc_w_load<true>(wv, d.w[0], I0, i0, IC, 4);
+                nf_cc_w_load<true, RUN>(wv, d.w[0], I0, i0, IC, 4);
                 __syncthreads();                        // readers of Wl / RS of the previous pass are done
-                nf_cc_w_store<true>(wv, Wl, WPs, 4);
+                nf_cc_w_store<true, RUN>(wv, Wl, WPs, 4);
             } else {
                 nf_cc_dma_wait();                       // (chunk 0 was requested in the l = 0 iteration, the others behind the previous K loop)
             }
@@ -2043,6 +2135,25 @@ __global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_
         }
     }
     NF_CC_STAMP(97);
+}
+
+template <int NPB, int NKQ, bool HALO, bool CPL, int FWc, int CSc, bool PK>
+__global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd(nf_convnet_bwd_desc d, NfCvGeo g, int I0, int O_out, int training,
+                                                                     NfSplit cs) {
+    nf_cc_bwd_step<NPB, NKQ, HALO, CPL, FWc, CSc, PK, false>(d, g, I0, O_out, training, cs);
+}
+
+// the steps of a run in BACKWARD order (the comment above k_convnet_chain_fwd_run)
+template <int NPB, int NKQ, int FWc, int CSc, bool PK>
+__global__ void __launch_bounds__(NF_CV_THREADS) k_convnet_chain_bwd_run(NfCcRunHead h0, NfCcRunBwdArgs a) {
+#pragma unroll 1
+    for (int s = 0; s < h0.n; ++s) {
+        NfCcRunHead h;
+        nf_cc_run_head(h);
+        h.cs.odd = a.d[s].cp_odd ? 1 : 0;
+        nf_cc_bwd_step<NPB, NKQ, false, true, FWc, CSc, PK, true>(a.d[s], h.g, h.I0, h.O_out, h.training, h.cs);
+        nf_cc_step_end();
+    }
 }
 
 // =====================================================================================================================================
@@ -2203,10 +2314,10 @@ extern "C" int nf_convnet_chain_ws_floats(int64_t B, int I0, int O_out, int H, i
     return (int)(2 * slots);
 }
 
-extern "C" int nf_convnet_chain_fwd(const nf_convnet_desc* desc, int64_t B, int I0, int O_out, int H, int W, int training,
-                                    float bn_eps, float bn_momentum, nf_stream_t stream) {
+// what a forward descriptor must satisfy at this shape (both entry points); fills the split map, the geometry and the tile
+static int nf_cc_fwd_args(const nf_convnet_desc* desc, int64_t B, int I0, int O_out, int H, int W, int training, NfSplit& cs, NfCvGeo& g,
+                          int& PX) {
     if (desc == nullptr || !nf_convnet_chain_usable(B, I0, O_out, H, W)) return NF_E_BADARG;
-    NfSplit cs;
     memset(&cs, 0, sizeof(cs));
     if (desc->cp_z != nullptr) {
         if (desc->cp_y == nullptr || desc->cp_ld == nullptr || desc->cp_a == nullptr || desc->cp_c == nullptr) return NF_E_BADARG;
@@ -2222,8 +2333,7 @@ extern "C" int nf_convnet_chain_fwd(const nf_convnet_desc* desc, int64_t B, int 
                   : (desc->hd_W == nullptr || desc->cp_C < 9 || desc->cp_C > 64))
             return NF_E_BADARG;
     }
-    NfCvGeo g;
-    const int PX = nf_cc_tile_px(B, H, W);
+    PX = nf_cc_tile_px(B, H, W);
     if (!nf_cv_geometry(g, B, H, W, 3, PX)) return NF_E_BADARG;
     if ((training || H * W > PX) && desc->ws_zero == nullptr) return NF_E_BADARG;     // exchange slots (statistics; halo rows)
     if (desc->hd_x != nullptr) {
@@ -2231,13 +2341,23 @@ extern "C" int nf_convnet_chain_fwd(const nf_convnet_desc* desc, int64_t B, int 
         const int rows = H * W > PX ? PX / W + 2 : H, ns = H * W > PX ? 1 : PX / (H * W);
         if ((int64_t)ns * I0 * rows * W > NF_CC_HD_X1_MAX || (H * W > PX && cs.W < 16)) return NF_E_BADARG;
     }
-    const int OCB = (O_out + 31) / 32;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = 0;
-    const bool cp = desc->cp_z != nullptr;
-    bool pk = desc->wpk[0] != nullptr;                  // all six images or none
+    const bool pk = desc->wpk[0] != nullptr;            // all six images or none
     for (int i = 1; i < NF_CC_NL; ++i)
         if ((desc->wpk[i] != nullptr) != pk) return NF_E_BADARG;
+    return 0;
+}
+
+extern "C" int nf_convnet_chain_fwd(const nf_convnet_desc* desc, int64_t B, int I0, int O_out, int H, int W, int training,
+                                    float bn_eps, float bn_momentum, nf_stream_t stream) {
+    NfSplit cs;
+    NfCvGeo g;
+    int PX = 0;
+    int rc = nf_cc_fwd_args(desc, B, I0, O_out, H, W, training, cs, g, PX);
+    if (rc) return rc;
+    const int OCB = (O_out + 31) / 32;
+    hipStream_t st = (hipStream_t)stream;
+    const bool cp = desc->cp_z != nullptr;
+    const bool pk = desc->wpk[0] != nullptr;
 #define NF_CC_FWD(NPB_, NKQ_, HALO_, CP_, FW_, CS_, PK_)                                                                                    \
     do {                                                                                                                                    \
         rc = nf_cc_optin(k_convnet_chain_fwd<NPB_, NKQ_, HALO_, CP_, FW_, CS_, PK_>);                                                       \
@@ -2274,10 +2394,69 @@ extern "C" int nf_convnet_chain_fwd(const nf_convnet_desc* desc, int64_t B, int 
     return 0;
 }
 
-extern "C" int nf_convnet_chain_bwd(const nf_convnet_bwd_desc* desc, int64_t B, int I0, int O_out, int H, int W, int training,
-                                    nf_stream_t stream) {
+// the whole-sample instantiations by tile and level geometry (the HALO = false rows of the single-step dispatch)
+#define NF_CC_RUN_DISPATCH(K)                                                   \
+    do {                                                                        \
+        if (PX == 256) K(8, 2, 0, 0);                                           \
+        else if (PX == 32) {                                                    \
+            if (g.FW == 6 && g.CS == 73) K(1, 16, 6, 73);                       \
+            else K(1, 16, 0, 0);                                                \
+        } else if (PX == 64) {                                                  \
+            if (g.FW == 10 && g.CS == 101) K(2, 8, 10, 101);                    \
+            else if (g.FW == 6 && g.CS == 145) K(2, 8, 6, 145);                 \
+            else K(2, 8, 0, 0);                                                 \
+        } else if (g.FW == 10 && g.CS == 201) K(4, 4, 10, 201);                 \
+        else if (g.FW == 6 && g.CS == 289) K(4, 4, 6, 289);                     \
+        else K(4, 4, 0, 0);                                                     \
+    } while (0)
+
+extern "C" int nf_convnet_chain_fwd_run(const nf_convnet_desc* descs, int n, int64_t B, int I0, int O_out, int H, int W, int training,
+                                        float bn_eps, float bn_momentum, nf_stream_t stream) {
+    if (descs == nullptr || n < 1 || n > NF_CONVNET_RUN_MAX) return NF_E_BADARG;
+    if (n == 1) return nf_convnet_chain_fwd(descs, B, I0, O_out, H, W, training, bn_eps, bn_momentum, stream);
+    NfSplit cs, cs_s;
+    NfCvGeo g;
+    int PX = 0;
+    for (int s = 0; s < n; ++s) {
+        const nf_convnet_desc& d = descs[s];
+        const int rc = nf_cc_fwd_args(&d, B, I0, O_out, H, W, training, s == 0 ? cs : cs_s, g, PX);
+        if (rc) return rc;
+        if (H * W > PX) return NF_E_BADARG;             // a sample over two workgroups: the next step would read another workgroup's rows
+        // the coupling and the head are what chains the steps inside the launch; one split map (but for the side), one weight form
+        if (d.cp_z == nullptr || d.hd_x == nullptr || d.cp_inverse) return NF_E_BADARG;
+        if (d.cp_mode != descs[0].cp_mode || d.cp_C != descs[0].cp_C || (d.wpk[0] != nullptr) != (descs[0].wpk[0] != nullptr))
+            return NF_E_BADARG;
+    }
+    const int OCB = (O_out + 31) / 32;
+    hipStream_t st = (hipStream_t)stream;
+    const bool pk = descs[0].wpk[0] != nullptr;
+    NfCcRunArgs a;
+    memcpy(a.d, descs, sizeof(nf_convnet_desc) * (size_t)n);
+    const NfCcRunHead h = {g, cs, n, I0, O_out, training, bn_eps, bn_momentum};
+    int rc = 0;
+#define NF_CC_FWD_RUN1(NPB_, NKQ_, FW_, CS_, PK_)                                                                                           \
+    do {                                                                                                                                    \
+        rc = nf_cc_optin(k_convnet_chain_fwd_run<NPB_, NKQ_, FW_, CS_, PK_>);                                                               \
+        if (rc == 0)                                                                                                                        \
+            hipLaunchKernelGGL((k_convnet_chain_fwd_run<NPB_, NKQ_, FW_, CS_, PK_>), dim3((unsigned)g.tiles), dim3(NF_CV_THREADS),          \
+                               (nf_cc_lds_bytes<NPB_, NKQ_>(g, OCB)), st, h, a);                                                          \
+    } while (0)
+#define NF_CC_FWD_RUN(NPB_, NKQ_, FW_, CS_)                                                                                                 \
+    do {                                                                                                                                    \
+        if (pk) NF_CC_FWD_RUN1(NPB_, NKQ_, FW_, CS_, true);                                                                                 \
+        else NF_CC_FWD_RUN1(NPB_, NKQ_, FW_, CS_, false);                                                                                   \
+    } while (0)
+    NF_CC_RUN_DISPATCH(NF_CC_FWD_RUN);
+#undef NF_CC_FWD_RUN
+#undef NF_CC_FWD_RUN1
+    if (rc) return rc;
+    NF_CHECK_LAUNCH();
+    return 0;
+}
+
+// what a backward descriptor must satisfy at this shape (both entry points)
+static int nf_cc_bwd_args(const nf_convnet_bwd_desc* desc, int64_t B, int I0, int O_out, int H, int W, NfSplit& cs, NfCvGeo& g, int& PX) {
     if (desc == nullptr || !nf_convnet_chain_usable(B, I0, O_out, H, W)) return NF_E_BADARG;
-    NfSplit cs;
     memset(&cs, 0, sizeof(cs));
     if (desc->cp_g_y != nullptr) {
         if (desc->cp_g_ld == nullptr || desc->cp_z == nullptr || desc->cp_out == nullptr || desc->cp_a == nullptr || desc->cp_c == nullptr ||
@@ -2287,8 +2466,7 @@ extern "C" int nf_convnet_chain_bwd(const nf_convnet_bwd_desc* desc, int64_t B, 
     } else if (desc->g_out == nullptr) {
         return NF_E_BADARG;
     }
-    NfCvGeo g;
-    const int PX = nf_cc_tile_px(B, H, W);
+    PX = nf_cc_tile_px(B, H, W);
     if (!nf_cv_geometry(g, B, H, W, 3, PX)) return NF_E_BADARG;
     if (desc->hd_g_h != nullptr) {                      // the next step's head transposed in the prologue (same shapes as the forward's)
         const bool small = desc->cp_C >= 2 && desc->cp_C <= 4;      // (thread per pixel; hd_W = the weight the forward saved)
@@ -2296,12 +2474,22 @@ extern "C" int nf_convnet_chain_bwd(const nf_convnet_bwd_desc* desc, int64_t B, 
             ((cs.H * cs.W) & 15) != 0 || (H * W > PX && cs.W < 16) || (int64_t)(O_out >> 1) * PX > NF_CC_HD_X1_MAX)
             return NF_E_BADARG;
     }
-    hipStream_t st = (hipStream_t)stream;
-    int rc = 0;
-    const bool cp = desc->cp_g_y != nullptr;
-    bool pk = desc->wpk[0] != nullptr;
+    const bool pk = desc->wpk[0] != nullptr;
     for (int i = 1; i < NF_CC_NL; ++i)
         if ((desc->wpk[i] != nullptr) != pk) return NF_E_BADARG;
+    return 0;
+}
+
+extern "C" int nf_convnet_chain_bwd(const nf_convnet_bwd_desc* desc, int64_t B, int I0, int O_out, int H, int W, int training,
+                                    nf_stream_t stream) {
+    NfSplit cs;
+    NfCvGeo g;
+    int PX = 0;
+    int rc = nf_cc_bwd_args(desc, B, I0, O_out, H, W, cs, g, PX);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const bool cp = desc->cp_g_y != nullptr;
+    const bool pk = desc->wpk[0] != nullptr;
 #define NF_CC_BWD(NPB_, NKQ_, HALO_, CP_, FW_, CS_, PK_)                                                                                    \
     do {                                                                                                                                    \
         rc = nf_cc_optin(k_convnet_chain_bwd<NPB_, NKQ_, HALO_, CP_, FW_, CS_, PK_>);                                                       \
@@ -2336,6 +2524,51 @@ extern "C" int nf_convnet_chain_bwd(const nf_convnet_bwd_desc* desc, int64_t B, 
     NF_CHECK_LAUNCH();
     return 0;
 }
+
+extern "C" int nf_convnet_chain_bwd_run(const nf_convnet_bwd_desc* descs, int n, int64_t B, int I0, int O_out, int H, int W,
+                                        int training, nf_stream_t stream) {
+    if (descs == nullptr || n < 1 || n > NF_CONVNET_RUN_MAX) return NF_E_BADARG;
+    if (n == 1) return nf_convnet_chain_bwd(descs, B, I0, O_out, H, W, training, stream);
+    NfSplit cs, cs_s;
+    NfCvGeo g;
+    int PX = 0;
+    for (int s = 0; s < n; ++s) {
+        const nf_convnet_bwd_desc& d = descs[s];
+        const int rc = nf_cc_bwd_args(&d, B, I0, O_out, H, W, s == 0 ? cs : cs_s, g, PX);
+        if (rc) return rc;
+        if (H * W > PX) return NF_E_BADARG;             // (as in the forward run)
+        if (d.cp_g_y == nullptr) return NF_E_BADARG;
+        // the first descriptor is the run's LAST step: its g_y comes from outside, with or without a head; the others chain by theirs
+        if (s >= 1 && (d.hd_g_h != nullptr) != (descs[n - 1].hd_g_h != nullptr)) return NF_E_BADARG;
+        if (d.cp_mode != descs[0].cp_mode || d.cp_C != descs[0].cp_C || (d.wpk[0] != nullptr) != (descs[0].wpk[0] != nullptr))
+            return NF_E_BADARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const bool pk = descs[0].wpk[0] != nullptr;
+    NfCcRunBwdArgs a;
+    memcpy(a.d, descs, sizeof(nf_convnet_bwd_desc) * (size_t)n);
+    const NfCcRunHead h = {g, cs, n, I0, O_out, training, 0.f, 0.f};
+    int rc = 0;
+#define NF_CC_BWD_RUN1(NPB_, NKQ_, FW_, CS_, PK_)                                                                                           \
+    do {                                                                                                                                    \
+        rc = nf_cc_optin(k_convnet_chain_bwd_run<NPB_, NKQ_, FW_, CS_, PK_>);                                                               \
+        if (rc == 0)                                                                                                                        \
+            hipLaunchKernelGGL((k_convnet_chain_bwd_run<NPB_, NKQ_, FW_, CS_, PK_>), dim3((unsigned)g.tiles), dim3(NF_CV_THREADS),          \
+                               (nf_cc_lds_bytes<NPB_, NKQ_>(g, 1)), st, h, a);                                                   \
+    } while (0)
+#define NF_CC_BWD_RUN(NPB_, NKQ_, FW_, CS_)                                                                                                 \
+    do {                                                                                                                                    \
+        if (pk) NF_CC_BWD_RUN1(NPB_, NKQ_, FW_, CS_, true);                                                                                 \
+        else NF_CC_BWD_RUN1(NPB_, NKQ_, FW_, CS_, false);                                                                                   \
+    } while (0)
+    NF_CC_RUN_DISPATCH(NF_CC_BWD_RUN);
+#undef NF_CC_BWD_RUN
+#undef NF_CC_BWD_RUN1
+    if (rc) return rc;
+    NF_CHECK_LAUNCH();
+    return 0;
+}
+#undef NF_CC_RUN_DISPATCH
 
 // ---- self-test of the three-way split (tests/test_gpu_ops.py::test_bf16_split_is_no_precision_reduction) ------------------------------
 // D[32][32] = A[32][K] * B[K][32] on ONE wave, K a multiple of 16: mode 0 = v_mfma_f32_32x32x2_f32 (the exact fp32 instruction),

@@ -8,6 +8,10 @@ Exact restatement of the module math in training mode (batch statistics, gradien
 statistics bookkeeping) and in evaluation mode.  The weight-norm arithmetic stays where it is: every convolution of a
 model gets its effective weight from ONE ``nf_weight_norm_fwd`` launch per pass (fused.weight_norm_all), the kernels
 here consume effective weights and return the gradient with respect to them.
+
+At the batches the reference trains with, the whole conditioner, its coupling and the step's Glow head are ONE persistent launch
+per direction (csrc/conv_chain.hip); _cn_forward and _cn_backward each have one such launch site, and both go through the run scope
+``ChainRuns``: the launches of consecutive flow steps of a level leave as one launch per direction where the kernels allow it.
 """
 import ctypes
 import functools
@@ -209,6 +213,7 @@ class ConvDefer:
         self.active, self.armed = CONV_DEFER_ON, False
         self.plu_jobs = []
         self.head_jobs = []
+        RUNS.reset()            # (chain launches a pass that raised left collected: their tensors are gone)
 
     def arm(self, weights):
         """fused.weight_norm_all: these effective weights' gradients are consumed by a backward that flushes first"""
@@ -286,6 +291,7 @@ class ConvDefer:
             _slab_sum_all(pending)
 
     def flush(self):
+        RUNS.flush()            # a run of backward chain launches that did not reach its first member is launched, not dropped
         layers, sums = self.layers, self.sums
         self.layers, self.sums, self.active, self.armed = [], [], False, False
         plu, self.plu_jobs = self.plu_jobs, []
@@ -335,6 +341,156 @@ def _chain_slots(n, dev):
     if gen >= (1 << 28):                                      # (8 gen + 7 stays a 32-bit tag)
         return WS.zeros(n, dev), 0
     return t, gen
+
+
+CHAIN_RUNS_ON = True           # (internal: False = one chain launch per flow step at every level, the form before the runs; tests compare)
+# Shortest run of flow steps that layers.Compose hands to a run scope.  A merged step boundary is worth about 3 us (C4: 0.27 ms over 94
+# boundaries, profiles/r21_chain_run.txt) and a run launch carries all NF_CONVNET_RUN_MAX descriptors in its arguments whatever its
+# length, so a pair of steps has nothing measurable to gain: it keeps its two launches, and with them the entry points that
+# tests/golden/compose_routes.json records for the two-step image Glow.
+CHAIN_RUN_MIN = 3
+
+
+class _RunRecord:
+    """one forward launch of a run of flow steps: ``n`` steps (known when the launch leaves); a member's backward finds it on its ctx"""
+    __slots__ = ('n', )
+
+    def __init__(self):
+        self.n = 0
+
+
+def _native_chain_launch(name, descs, args):
+    """``descs`` (ctypes descriptors of one shape, in launch order) as ONE launch: the single-step entry point ``name`` for one of
+    them -- the very call the steps made before there were runs -- else ``name``_run over the array"""
+    if len(descs) == 1:
+        N.call(name, ctypes.addressof(descs[0]), *args, N.stream())
+        return
+    size = ctypes.sizeof(descs[0])
+    arr = (type(descs[0]) * len(descs))()
+    for i, d in enumerate(descs):
+        ctypes.memmove(ctypes.addressof(arr) + i * size, ctypes.addressof(d), size)
+    N.call(name + '_run', ctypes.addressof(arr), len(descs), *args, N.stream())
+
+
+class ChainRuns:
+    """Consecutive flow steps of one level whose chain launches leave as ONE launch per direction (csrc/conv_chain.hip:
+    nf_convnet_chain_fwd_run / _bwd_run -- where a workgroup owns whole samples, step s + 1 reads of step s only what its own workgroup
+    wrote).  A run of k descriptors equals k single launches in the same order, so leaving early is always correct; what must not
+    happen is that something ELSE runs between two collected launches and reads what they have not written yet: every other native
+    launch flushes first (``before_call``, hooked into _native.call), and so does ConvDefer.flush.
+
+    Forward: ``with chain_run():`` around the steps (layers.Compose); a launch whose shape and mode match what is collected is
+    appended (the descriptor and the tensors it must keep alive), any other launch flushes and goes out as before.  Scope exit
+    launches.  Every member remembers (record, index) on its ctx.
+    Backward, inside a trainer step: the members of one record arrive in descending index order and are collected in arrival order;
+    the launch leaves when index 0 arrives, when anything else is launched, or at the end-of-pass flush."""
+
+    def __init__(self):
+        self.launcher = _native_chain_launch
+        self.busy = False
+        self.fwd_open = 0
+        self.reset()
+
+    def reset(self):
+        self.fwd, self.fwd_key, self.fwd_rec = [], None, None
+        self.bwd, self.bwd_key, self.bwd_rec, self.bwd_next = [], None, None, -1
+
+    @staticmethod
+    def _max():
+        return N.header_constant('NF_CONVNET_RUN_MAX')
+
+    def _leave(self, name, items, key):
+        self.busy = True
+        try:
+            self.launcher(name, [d for d, _ in items], key[:-1])      # (key: the entry point's arguments + the weight form)
+        finally:
+            self.busy = False
+
+    def flush_fwd(self):
+        items, key, rec = self.fwd, self.fwd_key, self.fwd_rec
+        self.fwd, self.fwd_key, self.fwd_rec = [], None, None
+        if items:
+            rec.n = len(items)
+            self._leave('nf_convnet_chain_fwd', items, key)
+
+    def flush_bwd(self):
+        items, key = self.bwd, self.bwd_key
+        self.bwd, self.bwd_key, self.bwd_rec, self.bwd_next = [], None, None, -1
+        if items:
+            self._leave('nf_convnet_chain_bwd', items, key)
+
+    def flush(self):
+        self.flush_fwd()
+        self.flush_bwd()
+
+    def before_call(self, name):
+        """_native.call, in front of every native launch"""
+        if (self.fwd or self.bwd) and not self.busy:
+            self.flush()
+
+    def launch_fwd(self, ctx, d, key, keep, chainable):
+        """the forward chain launch of one step: collected inside an open scope when ``chainable`` (whole-sample tiles, coupling and
+        head in the launch), else launched now"""
+        if not (CHAIN_RUNS_ON and self.fwd_open and chainable):
+            self.flush()
+            self._leave('nf_convnet_chain_fwd', [(d, keep)], key)
+            return
+        self.flush_bwd()
+        if self.fwd and (self.fwd_key != key or len(self.fwd) >= self._max()):
+            self.flush_fwd()
+        if not self.fwd:
+            self.fwd_key, self.fwd_rec = key, _RunRecord()
+        ctx.chain_run = (self.fwd_rec, len(self.fwd))
+        self.fwd.append((d, keep))
+
+    def launch_bwd(self, ctx, d, key, keep, collect, chained_in):
+        """the backward chain launch of one step.  ``collect``: inside a trainer step with direct gradient sinks (nothing but native
+        launches consumes what the launch writes); ``chained_in``: its g_y is computed in its own prologue from the previous
+        member's output (a member whose g_y came from elsewhere starts a collection of its own)"""
+        rec, idx = getattr(ctx, 'chain_run', None) or (None, -1)
+        if not (CHAIN_RUNS_ON and collect and rec is not None and rec.n > 1):
+            self.flush()
+            self._leave('nf_convnet_chain_bwd', [(d, keep)], key)
+            return
+        self.flush_fwd()
+        if self.bwd and not (self.bwd_rec is rec and self.bwd_key == key and self.bwd_next == idx and chained_in):
+            self.flush_bwd()
+        if not self.bwd:
+            self.bwd_key, self.bwd_rec = key, rec
+        self.bwd.append((d, keep))
+        self.bwd_next = idx - 1
+        if idx == 0:
+            self.flush_bwd()
+
+
+RUNS = ChainRuns()
+N._before_call = RUNS.before_call
+
+
+class chain_run:
+    """``with chain_run():`` -- the forward chain launches of the flow steps inside leave as one launch per run (ChainRuns)"""
+
+    def __enter__(self):
+        RUNS.fwd_open += 1
+        return self
+
+    def __exit__(self, *exc):
+        RUNS.fwd_open -= 1
+        if RUNS.fwd_open == 0:
+            if exc[0] is None:
+                RUNS.flush_fwd()
+            else:
+                RUNS.fwd, RUNS.fwd_key, RUNS.fwd_rec = [], None, None
+        return False
+
+
+def chain_run_ok(net, z, mode):
+    """a flow step on z can be a member of a run: its head rides its coupling's chain launch and a workgroup owns whole samples"""
+    if not (CHAIN_RUNS_ON and head_in_chain_ok(net, z, mode)):
+        return False
+    B, C, Hf, Wf = z.shape
+    I0, Hh, Ww = (C // 2, Hf, Wf) if mode == N.SPLIT_CHANNEL else (2 * C, Hf // 2, Wf // 2)
+    return _chain_ws_floats(B, I0, 2 * I0, Hh, Ww) <= N.header_constant('NF_CONVNET_WS_FLOATS')     # (more: the halo hand-over's slots)
 
 
 def _convnet_modules(net):
@@ -451,6 +607,7 @@ def _cn_forward(ctx, x, training, defer, tensors, cpl=None, packs=None):
         need = training or nws > N.header_constant('NF_CONVNET_WS_FLOATS')           # (halo hand-over: in evaluation mode too)
         slots, d.ws_gen = _chain_slots(nws, dev) if need else (None, 0)
         d.ws_zero = slots.data_ptr() if need else None
+        pend = None
         if cpl is not None:
             z, ld, a, c, mode, odd, inverse = cpl
             y = torch.empty_like(z)
@@ -473,7 +630,11 @@ def _cn_forward(ctx, x, training, defer, tensors, cpl=None, packs=None):
                 else:                          # (not the tensors this launch works on: the head runs on its own kernel first)
                     NF.PENDING_HEADS[z.data_ptr()] = pend
                     NF.flush_pending_head(z)
-        N.call('nf_convnet_chain_fwd', ctypes.addressof(d), B, I0, O_out, Hh, Ww, int(training), BN_EPS, BN_MOMENTUM, N.stream())
+        # the ONE forward chain launch site: inside a run scope a step whose head and coupling ride the launch on whole-sample tiles is
+        # collected (ChainRuns; everything the launch touches stays alive with it), any other launch leaves now
+        chainable = bool(d.hd_x) and not d.cp_inverse and nws <= N.header_constant('NF_CONVNET_WS_FLOATS')
+        RUNS.launch_fwd(ctx, d, (B, I0, O_out, Hh, Ww, int(training), BN_EPS, BN_MOMENTUM, packs is not None),
+                        (x, ws, acts, out, w, slots, cpl, y, packs, pend, tensors), chainable)
     else:
         if cpl is not None:
             raise RuntimeError('the fused coupling needs the chain kernel (coupling_fusable was not consulted)')
@@ -624,6 +785,7 @@ def _cn_backward(ctx, g_out, cpl_grads=None):
         if ctx.sinks is not None:                   # BatchNorm parameter gradients: added by the launch itself
             for j in range(nb):
                 d.g_gamma[j], d.g_beta[j] = ctx.sinks[nl + 2 * j].data_ptr(), ctx.sinks[nl + 2 * j + 1].data_ptr()
+        pend, g_z = None, None
         if cpl is not None:
             z, out, a, c = cpl
             g_y, g_ld = cpl_grads
@@ -651,7 +813,11 @@ def _cn_backward(ctx, g_out, cpl_grads=None):
                     d.hd_g_h, d.hd_W, d.hd_ls = hg.data_ptr(), hW.data_ptr(), hls.data_ptr()
                 else:
                     NF.flush_pending_head_bwd(pend)
-        N.call('nf_convnet_chain_bwd', ctypes.addressof(d), B, I0, O_out, Hh, Ww, int(training), N.stream())
+        # the ONE backward chain launch site: inside a trainer step, where every gradient goes to a sink or to the next native launch,
+        # the members of a forward run are collected and leave together (ChainRuns)
+        collect = bool(defer) and cpl is not None and ctx.cpl_sinks is not None
+        RUNS.launch_bwd(ctx, d, (B, I0, O_out, Hh, Ww, int(training), bool(d.wpk[0])),
+                        (saved, cpl_grads, g_out, gn, stores, acc, slots, g_z, g_x, pend, getattr(ctx, 'packs', None)), collect, bool(d.hd_g_h))
 
     layer(H, O_out, 1, nl - 1, in_=acts[nb - 1], weight=w[nl - 1], g_direct=g_out, gn_out=gn[nb - 1], sum_g=sums[nb - 1, 0],
           sum_gx=sums[nb - 1, 1], **in_bn(nb - 1))

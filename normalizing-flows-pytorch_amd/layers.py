@@ -241,11 +241,46 @@ class Compose(nn.Module):
             return (*FUSED.glow_step_vec(z, ld, a, c, k), 3)                      # the whole step: one launch
         return self._head_step(a, c, k, z, ld)
 
+    def _glow_chain_run(self, i, z, ld):
+        """consecutive image Glow steps of one shape where a workgroup of the chain kernels owns whole samples (the 8 x 8 and 4 x 4 levels
+        of the CIFAR pyramid): every step as in _head_step -- its own autograd nodes, its head left to its coupling's chain launch --
+        but the chain launches of the run leave as ONE (fused_conv.chain_run).  Declines, and the per-step routes serve, for fewer than
+        fused_conv.CHAIN_RUN_MIN steps, while a
+        member's ActNorm awaits its initialisation, when the members' conditioners are not of one training mode, when a head would
+        not ride its chain launch, and on the halo hand-over shapes (16 x 16 maps on two tiles per sample)."""
+        from . import fused_conv as FC
+        if not (FC.CHAIN_RUNS_ON and GLOW_HEAD_W_ON and HEAD_IN_CHAIN and z.dim() == 4 and z.shape[1] > NF.HEAD_MAX_C and z.is_contiguous()):
+            return None
+        first = []
+
+        def member(j, z):
+            m = self._glow_triple_at(j, z)
+            if m is None:
+                return None
+            a, c, k = m
+            if not (a.initialized and type(k) is AffineCoupling and isinstance(k.net, ConvNet) and c._W_eff is not None
+                    and k.mode in (N.SPLIT_CHANNEL, N.SPLIT_CHECKER) and (not first or (k.net.training, k.mode) == first[0])
+                    and NF.glow_head_w_usable(z, k.mode) and FC.chain_run_ok(k.net, z, k.mode)):
+                return None
+            first.append((k.net.training, k.mode))
+            return m
+        run = self._collect(i, z, 1, 3, member)
+        if len(run) < FC.CHAIN_RUN_MIN:                            # (a pair of steps keeps its two launches: nothing measurable to gain)
+            return None
+        with FC.chain_run():
+            for a, c, k in run:
+                out = self._head_step(a, c, k, z, ld)
+                if out is None:
+                    raise RuntimeError('a member of a run of Glow steps declined its fused head (the route tested the same conditions)')
+                z, ld = out[:2]
+        return z, ld, 3 * len(run)
+
     def _glow_step_w(self, i, z, ld):
         """image data with more channels than the in-kernel PLU head takes (9 .. 64): head in one MFMA launch"""
         m = self._glow_triple_at(i, z) if GLOW_HEAD_W_ON and z.dim() == 4 and z.shape[1] > NF.HEAD_MAX_C else None
         if m is not None:
-            return self._head_step(*m, z, ld)
+            # (the run of such steps first: part of this route, not an entry of its own -- the route list is the documented order)
+            return self._glow_chain_run(i, z, ld) or self._head_step(*m, z, ld)
 
     @staticmethod
     def _actnorm_init(a, z):
