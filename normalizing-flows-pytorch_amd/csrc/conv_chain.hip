@@ -48,22 +48,34 @@ static_assert(2 * NF_CC_STAT_SLOTS == NF_CONVNET_WS_FLOATS, "exchange workspace 
 NF_PERSIST_STATE(nf_cc)
 NF_PERSIST_HOST_API(nf_cc)
 
-// phase stamps of workgroup 0 (tools/probes/chain_prof.py builds this file with -DNF_CC_PROF=1; 100 MHz wall clock)
+// phase stamps of workgroup 0 (tools/probes/chain_prof.py builds this file with -DNF_CC_PROF=1; 100 MHz wall clock).
+// -DNF_CC_PROF=2: no phase stamps, nothing that only workgroup 0 does -- every workgroup records when it reaches the poll of every
+// exchange round, forward and backward: nf_cc_arrive[direction][round][workgroup] (NF_CC_PROF=1 records round 1 of the forward only)
 #ifdef NF_CC_PROF
 __device__ long long nf_cc_prof[128];
-__device__ long long nf_cc_arrive[128];
+__device__ long long nf_cc_arrive[2 * NF_CC_NB * NF_CC_MAX_BLOCKS];
 extern "C" int nf_cc_arrive_read(long long* out) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(nf_cc_arrive), sizeof(long long) * 128);
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(nf_cc_arrive), sizeof(long long) * 2 * NF_CC_NB * NF_CC_MAX_BLOCKS);
 }
+#define NF_CC_ARRIVE(dir, round)                                                                                            \
+    do {                                                                                                                    \
+        if ((NF_CC_PROF == 2 || ((dir) == 0 && (round) == 1)) && threadIdx.x == 0)                                          \
+            nf_cc_arrive[((dir) * NF_CC_NB + (round)) * NF_CC_MAX_BLOCKS + blockIdx.x] = wall_clock64();                    \
+    } while (0)
+#if NF_CC_PROF == 1
 #define NF_CC_STAMP(i)                                                                 \
     do {                                                                               \
         if (blockIdx.x == 0 && threadIdx.x == 0) nf_cc_prof[i] = wall_clock64();       \
     } while (0)
+#else
+#define NF_CC_STAMP(i)
+#endif
 extern "C" int nf_cc_prof_read(long long* out) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(nf_cc_prof), sizeof(long long) * 128);
 }
 #else
 #define NF_CC_STAMP(i)
+#define NF_CC_ARRIVE(dir, round)
 #endif
 
 // threadIdx.x as the helpers below read it.  RUN = false (the single-step kernels): the register itself.  RUN = true (a step of
@@ -92,8 +104,9 @@ __device__ __forceinline__ unsigned nf_cc_tidx() {
 // two slots of a PAIR (2 p, 2 p + 1) -- always the same tap, neighbouring octets, so every operand address is base(hs) + literal.
 
 struct NfCcLds {            // offsets in floats
-    int FA, WL, RS, KC, KB, RED, TOT, BNV, total, WPs;
+    int FA, WL, RS, KC, KB, RED, TOT, BNV, ST, total, WPs;
 };
+#define NF_CC_ST_FLOATS (NF_CC_NB * 3 * 32)             // the larger of the two stashes below (backward: NF_CC_NB * 64)
 template <int NPB, int NKQ>
 __host__ __device__ inline NfCcLds nf_cc_lds(int CS, int OCB) {
     NfCcLds L;
@@ -114,6 +127,10 @@ __host__ __device__ inline NfCcLds nf_cc_lds(int CS, int OCB) {
     // level but 4 x 4): a global load at each layer's top is ~0.7 us of exposed latency on the serial chain
     L.BNV = (L.total + NF_CC_NB * 128) * (int)sizeof(float) <= 160 * 1024 ? L.total : -1;
     if (L.BNV >= 0) L.total += NF_CC_NB * 128;
+    // workgroup 0's bookkeeping of a step, kept until ONE pass writes it out (same rule: only where the geometry leaves room).  Forward
+    // st[layer][mean | invstd | unbiased variance][32]: saved constants and running statistics; backward st[layer][sum gn | sum gn xhat][32]
+    L.ST = (L.total + NF_CC_ST_FLOATS) * (int)sizeof(float) <= 160 * 1024 ? L.total : -1;
+    if (L.ST >= 0) L.total += NF_CC_ST_FLOATS;
     (void)OCB;
     return L;
 }
@@ -575,9 +592,7 @@ __device__ __forceinline__ bool nf_cc_stats_exchange(float* sm, const NfCcLds& L
     const unsigned long long* rs = slots + (size_t)round * NF_CC_MAX_BLOCKS * 64;
     const unsigned gen = gbase + (unsigned)(round + 1);
     if (round == 1) NF_CC_STAMP(57);
-#ifdef NF_CC_PROF
-    if (round == 1 && nf_cc_tidx<RUN>() == 0) nf_cc_arrive[blockIdx.x] = wall_clock64();
-#endif
+    NF_CC_ARRIVE(0, round);
     const int XS = 65;
     const int lane = nf_cc_tidx<RUN>() & 63, ci = 2 * (nf_cc_tidx<RUN>() >> 6) + (lane >> 5), l = lane & 31;
     float S, M2;
@@ -1202,6 +1217,9 @@ __device__ __forceinline__ void nf_cc_fwd_step(const nf_convnet_desc& d, const N
 
     constexpr bool packed = PK;                         // compile-time: the weights arrive as LDS images (nf_conv_weight_pack)
     constexpr bool cpl = CPL;                           // the coupling rides the epilogue of the output convolution (d.cp_z != NULL)
+    // workgroup 0 keeps its bookkeeping in LDS where there is room (nf_cc_lds): a literal in the per-level instantiations, block-uniform
+    const int ST = nf_cc_lds<NPB, NKQ>(CSr, OCB).ST;
+    const bool stash = ST >= 0;
     NF_CC_STAMP(0);
     // ---- the step's head (ActNorm + 1 x 1 convolution) rides the prologue: its operands are requested before anything else ----------
 #ifdef NF_CC_NO_HEAD_FWD                                 // (probe builds: what the prologue's code costs the rest of the kernel in registers)
@@ -1376,7 +1394,13 @@ __device__ __forceinline__ void nf_cc_fwd_step(const nf_convnet_desc& d, const N
                 const float sc = kb[32 + k] * invstd;
                 kc[k] = sc;
                 kc[32 + k] = kb[64 + k] - mean * sc;
-                if (blockIdx.x == 0) {
+                if (blockIdx.x == 0 && stash) {         // kept in LDS: nothing between two exchanges waits for memory (written out below)
+                    const float unb = Npx > 1 ? var * ((float)Npx / (float)(Npx - 1)) : var;
+                    float* st = sm + ST + 96 * l;
+                    st[k] = mean;
+                    st[32 + k] = invstd;
+                    st[64 + k] = unb;
+                } else if (blockIdx.x == 0) {
                     d.save_mean[l][k] = mean;
                     d.save_invstd[l][k] = invstd;
                     const float unb = Npx > 1 ? var * ((float)Npx / (float)(Npx - 1)) : var;
@@ -1464,6 +1488,20 @@ __device__ __forceinline__ void nf_cc_fwd_step(const nf_convnet_desc& d, const N
     // O_out multiply with zeros
     const int Ch = O_out >> 1;
     const bool packed5 = packed && cpl;                 // the packed 1 x 1 image has the row order of the fused coupling
+    // Workgroup 0's bookkeeping of all five layers in ONE pass: lanes < 32 of wave l take (layer l, channel lane) -- the layer is
+    // wave-uniform, so its descriptor pointers are scalar loads.  The old running statistics are requested here, in front of a wait for
+    // memory that every workgroup has anyway, and every store follows it: one round trip per step, none between two exchanges.
+    const int fl = __builtin_amdgcn_readfirstlane(wid);
+    const bool flush = stash && training && blockIdx.x == 0 && fl < NF_CC_NB && lane < 32;
+    float o_rm = 0.f, o_rv = 0.f;
+    int64_t o_nbt = 0;
+    int64_t* nbtp = nullptr;
+    if (flush) {
+        o_rm = d.rmean[fl][lane];
+        o_rv = d.rvar[fl][lane];
+        if (lane == 0) nbtp = d.nbt[fl];
+        if (nbtp != nullptr) o_nbt = nbtp[0];
+    }
     if (packed5) nf_cc_dma_wait();
     for (int e = nf_cc_tidx<RUN>(); e < (packed5 ? 0 : 32 * OCB * 4); e += NF_CV_THREADS) {
         const int row = e >> 2, o = e & 3;              // staged row -> the output channel it holds; octet o of its 32 input channels
@@ -1478,6 +1516,15 @@ __device__ __forceinline__ void nf_cc_fwd_step(const nf_convnet_desc& d, const N
         const float4 hi = oc < O_out ? *(const float4*)(d.w[5] + oc * 32 + 8 * o + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
         v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
         nf_cc_w_put8(Wl, WPs, 4 * (row >> 5) + o, row & 31, v);
+    }
+    if (flush) {                                        // (the stash was complete at the barrier behind layer 4's constants)
+        const float* st = sm + ST + 96 * fl;
+        const float mean = st[lane], unb = st[64 + lane];
+        d.save_mean[fl][lane] = mean;
+        d.save_invstd[fl][lane] = st[32 + lane];
+        d.rmean[fl][lane] = (1.f - mom) * o_rm + mom * mean;
+        d.rvar[fl][lane] = (1.f - mom) * o_rv + mom * unb;
+        if (nbtp != nullptr) nbtp[0] = o_nbt + 1;
     }
     __syncthreads();
     float ls = 0.f;                                     // this lane's part of its sample's sum of scales
@@ -1495,21 +1542,39 @@ __device__ __forceinline__ void nf_cc_fwd_step(const nf_convnet_desc& d, const N
                 if (pv && oc < O_out) d.out[(b * O_out + oc) * g.HW + q] = a5[r] + d.b[5][oc];
             }
         } else {
+            // The lane's eight elements in two batches of four (eight at once cost the kernels of the 16 x 16 level spilled registers):
+            // EVERY load of a batch -- z and the two biases of the 1 x 1 -- is requested before its first store, one memory round trip
+            // per batch.  Left to itself the compiler keeps a load behind every store it cannot tell apart from it, and the wait for
+            // that load drains the stores too: a round trip per element.  The loads may pass the stores: element o is read and written
+            // by this lane only, and different elements are different addresses -- so no store of this loop changes what a later load
+            // of it returns, whether or not the caller passes cp_y == cp_z.
 #pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                const int m = 16 * ob + (nf_cv_cd_row(r, hs) >> 1);
-                if (pv && m < Ch) {
-                    const float t = a5[r] + d.b[5][m], sr = a5[r + 1] + d.b[5][Ch + m];
-                    const float th = tanhf(sr), sv = th * ca + cc;
-                    const float es = expf(d.cp_inverse ? -sv : sv);
-                    // what the backward needs of the conditioner's output is exp(s) and tanh(raw): `out` is private to the fused
-                    // coupling, so they are what it keeps (8 of 256 compute units redo 12 k transcendentals otherwise)
-                    d.out[(b * O_out + m) * g.HW + q] = es;
-                    d.out[(b * O_out + Ch + m) * g.HW + q] = th;
-                    const int64_t o = b * cs.n_full + nf_cc_half_to_full(cs, 0, m, (int)q, lgw);
-                    const float z0 = d.cp_z[o];
-                    d.cp_y[o] = d.cp_inverse ? es * (z0 - t) : z0 * es + t;
-                    ls += sv;
+            for (int r0 = 0; r0 < 16; r0 += 8) {
+                float z4[4], bt4[4], bs4[4];
+#pragma unroll
+                for (int r = r0; r < r0 + 8; r += 2) {
+                    const int m = 16 * ob + (nf_cv_cd_row(r, hs) >> 1), i = (r - r0) >> 1;
+                    const bool ok = pv && m < Ch;
+                    z4[i] = ok ? d.cp_z[b * cs.n_full + nf_cc_half_to_full(cs, 0, m, (int)q, lgw)] : 0.f;
+                    bt4[i] = ok ? d.b[5][m] : 0.f;
+                    bs4[i] = ok ? d.b[5][Ch + m] : 0.f;
+                }
+#pragma unroll
+                for (int r = r0; r < r0 + 8; r += 2) {
+                    const int m = 16 * ob + (nf_cv_cd_row(r, hs) >> 1), i = (r - r0) >> 1;
+                    if (pv && m < Ch) {
+                        const float t = a5[r] + bt4[i], sr = a5[r + 1] + bs4[i];
+                        const float th = tanhf(sr), sv = th * ca + cc;
+                        const float es = expf(d.cp_inverse ? -sv : sv);
+                        // what the backward needs of the conditioner's output is exp(s) and tanh(raw): `out` is private to the fused
+                        // coupling, so they are what it keeps (8 of 256 compute units redo 12 k transcendentals otherwise)
+                        d.out[(b * O_out + m) * g.HW + q] = es;
+                        d.out[(b * O_out + Ch + m) * g.HW + q] = th;
+                        const int64_t o = b * cs.n_full + nf_cc_half_to_full(cs, 0, m, (int)q, lgw);
+                        const float z0 = z4[i];
+                        d.cp_y[o] = d.cp_inverse ? es * (z0 - t) : z0 * es + t;
+                        ls += sv;
+                    }
                 }
             }
         }
@@ -1734,6 +1799,7 @@ __device__ __forceinline__ const float* nf_cc_sum_exchange(float* sm, const NfCc
     const unsigned long long* rs = slots + (size_t)round * NF_CC_MAX_BLOCKS * 64;
     const int lane = nf_cc_tidx<RUN>() & 63, ci = 2 * (nf_cc_tidx<RUN>() >> 6) + (lane >> 5), l = lane & 31;
     int nrows = G;
+    NF_CC_ARRIVE(1, round);
     if (NF_CC_MAX_BLOCKS > NF_CC_FLAT_MAX && G > NF_CC_FLAT_MAX) {     // two levels, as in the forward kernel's statistics exchange
         const int grp = blockIdx.x / NF_CC_GROUP;
         unsigned long long* gs = slots + NF_CC_WG_SLOTS + (size_t)round * NF_CC_MAX_GROUPS * 64;
@@ -1820,6 +1886,9 @@ __device__ __forceinline__ void nf_cc_bwd_step(const nf_convnet_bwd_desc& d, con
     for (int e = nf_cc_tidx<RUN>(); e < 3 * NF_CC_FP(g.CS); e += NF_CV_THREADS) sm[L.FA + e] = 0.f;
     float* Fr = sm + L.FA;                              // ONE frame: G_l is written over G_{l+1} after every wave has left the K loop
     const bool bnv = L.BNV >= 0;                        // block-uniform
+    // workgroup 0 keeps the sums of the layers in LDS until one pass writes them out, where there is room (as in the forward kernel)
+    const int ST = nf_cc_lds<NPB, NKQ>(CSr, 1).ST;
+    const bool stash = ST >= 0;
     constexpr bool packed = PK;                         // compile-time: transposed weight images (nf_conv_weight_pack)
     const int nch0 = (I0 + 31) / 32;                    // a 3 x 3 layer's buffer: its forward images, then the transposed ones
     if (packed) nf_cc_dma_image(Wl, d.wpk[5] + NF_CONV_PACK_IMAGE_FLOATS, wid, lane);
@@ -1871,31 +1940,56 @@ __device__ __forceinline__ void nf_cc_bwd_step(const nf_convnet_bwd_desc& d, con
 #pragma unroll 1
         for (int pi = p0; pi < p0 + np; ++pi) {
             float bv[8];                                // this lane's eight K values: output channels 16 pi + 8 hs + j of its pixel
+            if (cpl) {
+                // The eight elements in two batches of four (eight at once cost the 8 x 8 run kernel spilled registers).  First pass:
+                // EVERY load of the batch in flight together (nothing for a lane or an element that takes nothing).  Left to itself
+                // the compiler keeps a load behind every store it cannot tell apart from it, and the wait for that load drains the
+                // stores too: a round trip per element.  The loads may pass the stores: element o of cp_g_z / cp_g_out is written
+                // by this lane only, in this iteration only, and different elements are different addresses -- no store of the
+                // second pass changes what a load of the first returns, whatever buffers the caller lets coincide.
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int oc = 16 * pi + 8 * hs + j;
-                const bool ok = pv && oc < O_out;
-                float v = 0.f;
-                if (!cpl) {
-                    v = ok ? go[(int64_t)oc * g.HW] : 0.f;
-                } else if (ok) {                        // the coupling's backward produces the conditioner's output gradient on the fly
-                    const bool is_s = oc >= Ch;
-                    const int m = is_s ? oc - Ch : oc;
-                    const int64_t o = b * cs.n_full + nf_cc_half_to_full(cs, 0, m, (int)q, lgw);
-                    const float gy0 = hbw ? RS[NF_CC_HD_X1 + m * PXW + px] : d.cp_g_y[o];
-                    v = gy0;                            // gradient of the shift
-                    if (is_s) {                         // cp_out = [exp(s) | tanh(raw)], left by the forward launch
-                        const float th = d.cp_out[(b * O_out + oc) * g.HW + q];
-                        const float es = d.cp_out[(b * O_out + m) * g.HW + q];
-                        d.cp_g_z[o] = gy0 * es;
-                        const float gs = gy0 * d.cp_z[o] * es + gl;
-                        v = gs * ca * (1.f - th * th);
-                        acc_a += gs * th;
-                        acc_c += gs;
+                for (int j0 = 0; j0 < 8; j0 += 4) {
+                    float gy4[4], th4[4], es4[4], z4[4];
+#pragma unroll
+                    for (int j = j0; j < j0 + 4; ++j) {
+                        const int oc = 16 * pi + 8 * hs + j;
+                        const bool ok = pv && oc < O_out, is_s = oc >= Ch;
+                        const int m = is_s ? oc - Ch : oc;
+                        const int64_t o = b * cs.n_full + nf_cc_half_to_full(cs, 0, m, (int)q, lgw);
+                        gy4[j - j0] = ok ? (hbw ? RS[NF_CC_HD_X1 + m * PXW + px] : d.cp_g_y[o]) : 0.f;
+                        th4[j - j0] = (ok && is_s) ? d.cp_out[(b * O_out + oc) * g.HW + q] : 0.f;
+                        es4[j - j0] = (ok && is_s) ? d.cp_out[(b * O_out + m) * g.HW + q] : 0.f;
+                        z4[j - j0] = (ok && is_s) ? d.cp_z[o] : 0.f;
                     }
-                    d.cp_g_out[(b * O_out + oc) * g.HW + q] = v;   // the deferred weight-gradient pass of the 1 x 1 convolution reads it
+                    // Second pass: the arithmetic and the stores, element by element in the order of the sums
+#pragma unroll
+                    for (int j = j0; j < j0 + 4; ++j) {
+                        const int oc = 16 * pi + 8 * hs + j;
+                        const bool ok = pv && oc < O_out, is_s = oc >= Ch;
+                        float v = 0.f;
+                        if (ok) {                       // the coupling's backward produces the conditioner's output gradient on the fly
+                            const int m = is_s ? oc - Ch : oc;
+                            const float gy0 = gy4[j - j0];
+                            v = gy0;                    // gradient of the shift
+                            if (is_s) {                 // cp_out = [exp(s) | tanh(raw)], left by the forward launch
+                                const float th = th4[j - j0], es = es4[j - j0];
+                                d.cp_g_z[b * cs.n_full + nf_cc_half_to_full(cs, 0, m, (int)q, lgw)] = gy0 * es;
+                                const float gs = gy0 * z4[j - j0] * es + gl;
+                                v = gs * ca * (1.f - th * th);
+                                acc_a += gs * th;
+                                acc_c += gs;
+                            }
+                            d.cp_g_out[(b * O_out + oc) * g.HW + q] = v;   // the deferred weight-gradient pass of the 1 x 1 convolution reads it
+                        }
+                        bv[j] = v;
+                    }
                 }
-                bv[j] = v;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int oc = 16 * pi + 8 * hs + j;
+                    bv[j] = (pv && oc < O_out) ? go[(int64_t)oc * g.HW] : 0.f;
+                }
             }
             bf16x8 bh, bm, bl;
 #pragma unroll
@@ -2017,7 +2111,9 @@ __device__ __forceinline__ void nf_cc_bwd_step(const nf_convnet_bwd_desc& d, con
                 if (halo) nf_cc_halo_peek(hw, hslots, l, g, (int)tile, y0);
             });
             NF_CC_STAMP(68 + 6 * (4 - l));
-            if (blockIdx.x == 0 && nf_cc_tidx<RUN>() < 64) {
+            if (stash) {                                // kept in LDS, written out in one pass behind layer 0 (below): nothing waits here
+                if (blockIdx.x == 0 && nf_cc_tidx<RUN>() < 64) sm[ST + 64 * l + nf_cc_tidx<RUN>()] = tot[nf_cc_tidx<RUN>()];
+            } else if (blockIdx.x == 0 && nf_cc_tidx<RUN>() < 64) {
                 (nf_cc_tidx<RUN>() < 32 ? d.sum_g[l] : d.sum_gx[l])[nf_cc_tidx<RUN>() & 31] = tot[nf_cc_tidx<RUN>()];
                 // the sums ARE the gradients of beta (sum gn) and gamma (sum gn xhat): straight into the caller's accumulators
                 float* sink = nf_cc_tidx<RUN>() < 32 ? d.g_beta[l] : d.g_gamma[l];
@@ -2090,8 +2186,28 @@ __device__ __forceinline__ void nf_cc_bwd_step(const nf_convnet_bwd_desc& d, con
     }
     NF_CC_STAMP(96);
 
+    // Workgroup 0 writes the sums of all five layers out in ONE pass, behind the first barrier of the passes below, where no exchange
+    // is left for anybody to wait at: wave l takes layer l, lanes < 32 sum gn (-> g_beta), the others sum gn xhat (-> g_gamma) -- the
+    // layer is wave-uniform, so its descriptor pointers are scalar loads.  Loads first, then the stores: one round trip per step.
+    // (Requesting the accumulators' old values in front of that barrier cost the 16 x 16 kernel spilled registers.)
+    auto flush = [&] {
+        const int fl = __builtin_amdgcn_readfirstlane(wid);
+        if (stash && blockIdx.x == 0 && fl < NF_CC_NB) {
+            float* sink = lane < 32 ? d.g_beta[fl] : d.g_gamma[fl];
+            const float old = sink != nullptr ? sink[c32] : 0.f;
+            const float tv = sm[ST + 64 * fl + lane];
+            (lane < 32 ? d.sum_g[fl] : d.sum_gx[fl])[c32] = tv;
+            // the sums ARE the gradients of beta (sum gn) and gamma (sum gn xhat): straight into the caller's accumulators
+            if (sink != nullptr) sink[c32] = old + tv;
+        }
+    };
     // ---- gradient of the conditioner's input: convolution 0 transposed, 32 input channels per pass ----
-    if (d.g_x != nullptr || cpl) {
+    if (!(d.g_x != nullptr || cpl)) {
+        if (stash) {                                    // (block-uniform)
+            __syncthreads();                            // the stash of layer 0 is written
+            flush();
+        }
+    } else {
         for (int i0 = 0; i0 < I0; i0 += 32) {
             const int IC = min(32, I0 - i0);
             if (!packed) {
@@ -2103,6 +2219,7 @@ __device__ __forceinline__ void nf_cc_bwd_step(const nf_convnet_bwd_desc& d, con
                 nf_cc_dma_wait();                       // (chunk 0 was requested in the l = 0 iteration, the others behind the previous K loop)
             }
             __syncthreads();
+            if (i0 == 0) flush();
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
             float gyv[OWN];                             // pass-through gradient of the untouched half: in flight under the K loop
